@@ -8,7 +8,7 @@ training step in the timed region: input normalisation (u8 NCHW -> bf16 NHWC
 kernel), forward, softmax-CE, backward (DDP bucketed all-reduce over RCCL when
 N > 1), fused SGD-momentum step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
 ``--gpus N`` without a torchrun environment launches the N ranks itself (a
@@ -16,10 +16,17 @@ N > 1), fused SGD-momentum step.
 under torchrun ``--gpus`` must equal WORLD_SIZE.
 
 Rank 0 prints ONE JSON line; `value` = total images/s over all ranks, timed
-as the MAX over ranks of K steps bracketed by barrier + device sync.  With N > 1 a
-second timed phase of the same K steps runs the reference's cross-replica BN
-(SyncBN on its own RCCL communicator) and reports it as ``syncbn_value``; the
-headline ``value`` is local BN (per-GPU batch 4096: 156 GB of the 288 GB HBM).
+as the MAX over ranks of K steps bracketed by barrier + device sync.  A plain run
+sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints the line.
+With ``--dump-outputs`` the last timed step starts again from the seeded initial
+weights (restored outside the timed region) and the run replays recorded autotuner
+decisions for the headline shapes instead of timing them, so the arrays depend on
+the seeded inputs alone and two runs, or two builds, can be compared array for array.
+With ``--full`` and N > 1 a second timed phase of the same K steps runs the
+reference's cross-replica BN (SyncBN on its own RCCL communicator) and reports it
+as ``syncbn_value``, followed by the peer-memory SyncBN phase, the bucket telemetry
+and the collective probe; the headline ``value`` is local BN (per-GPU batch 4096:
+156 GB of the 288 GB HBM).
 """
 from __future__ import annotations
 
@@ -65,9 +72,9 @@ def parse(argv=None):
     ap.add_argument("--syncbn", action="store_true",
                     help="headline phase with cross-replica BN (reference default); off = local BN")
     ap.add_argument("--no-syncbn-phase", dest="syncbn_phase", action="store_false",
-                    help="N > 1: skip the second, SyncBN-timed phase")
+                    help="--full, N > 1: skip the second, SyncBN-timed phase")
     ap.add_argument("--no-syncbn-peer", dest="syncbn_peer", action="store_false",
-                    help="N > 1: skip the third phase, SyncBN over the peer-memory mailboxes (parallel/peer.py)")
+                    help="--full, N > 1: skip the third phase, SyncBN over the peer-memory mailboxes (parallel/peer.py)")
     ap.add_argument("--syncbn-shared-group", action="store_true",
                     help="SyncBN collectives on the gradient communicator instead of their own "
                          "(DCP_SYNCBN_SHARED_GROUP=1; parallel/ddp.py bn_process_group)")
@@ -80,15 +87,29 @@ def parse(argv=None):
                          "torch: DistributedDataParallel's C++ Reducer")
     ap.add_argument("--force-ddp", action="store_true",
                     help="1 GPU: still run the data-parallel path -- a world-size-1 RCCL process group, the DDP "
-                         "engine, the SyncBN phase and telemetry (measures the engine's own cost and its HIP-graph "
+                         "engine and, with --full, the SyncBN phase and telemetry (measures the engine's own cost and its HIP-graph "
                          "capture on one box)")
     ap.add_argument("--telemetry-steps", type=int, default=5,
-                    help="N > 1, dcp engine: untimed steps after the timed phase that record per-bucket HIP events "
+                    help="--full, N > 1, dcp engine: untimed steps after the timed phase that record per-bucket HIP events "
                          "(exposed communication per rank)")
     ap.add_argument("--no-comm-probe", dest="comm_probe", action="store_false",
-                    help="distributed runs: skip the untimed collective probe after the timed phases (RCCL "
+                    help="--full, distributed runs: skip the untimed collective probe after the timed phases (RCCL "
                          "all-reduce bus bandwidth per bucket size; SyncBN-sized all-gather / all-reduce latency)")
     ap.add_argument("--lr", type=float, default=0.1)
+    ap.add_argument("--full", action="store_true",
+                    help="distributed runs: after the headline also run the diagnostic phases (bucket telemetry, "
+                         "the SyncBN and peer-memory SyncBN timed phases, the collective probe); a plain run "
+                         "measures the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32): the "
+                         "loss, the gradients, the updated parameters and the BN running statistics (a fixed, "
+                         "seeded sample of each where it is larger than DUMP_MAX_ELEMS values).  To be the same "
+                         "every run, that step starts again from the seeded initial weights and zero momentum "
+                         "(restored between two timed stretches): the arrays are those of a FIRST training step, "
+                         "and show nothing that appears only after an update, momentum accumulation included; "
+                         "and the headline shapes run recorded autotuner decisions (DUMP_TUNE_CACHE) instead of "
+                         "timing them.  The extra barrier + sync bracket counts in ms_per_step (visible only at "
+                         "toy sizes)")
     ap.add_argument("--profile-dir", default=None, help="write a torch.profiler trace here")
     ap.add_argument("--graph", dest="graph", action="store_true", default=None,
                     help="capture the whole step in a HIP graph and replay it (default on one GPU: +0.5 %% at the "
@@ -202,6 +223,112 @@ def comm_probe(dev, world, bn_group, reps=5):
     return out
 
 
+# --dump-outputs: the autotuner's decisions for the headline shapes (r50, per-GPU batch 4096),
+# recorded from one run with DCP_TUNE_CACHE and replayed, so every dumping run launches the same
+# kernels.  Timing picks between near-ties differently from run to run, the candidates' BN
+# statistics differ in their last bits, and the backward of a random-init ResNet-50 turns that into
+# 32 % (relative L2) of the gradients.  Shapes not listed (other configs, other batches) are still
+# tuned by timing; the run says so on stderr and in the line's "dump_tuning".  The entries are
+# indices into the candidate tables (kTgCfgs in csrc/conv_igemm.hip, kWgCfgs in csrc/bindings.cpp):
+# the file's first line holds their fingerprint, and a table edited since is refused until the
+# file is recorded again (DCP_TUNE_CACHE=<file> python bench.py, then sort it and put the
+# "# candidate tables <fingerprint>" line first).  (The 32 % is one pair of runs.)
+DUMP_TUNE_CACHE = os.path.join(ROOT, "ddp_classification_pytorch_amd", "bench_dump_tuning.txt")
+
+
+def candidate_tables_fingerprint():
+    """sha256 (16 hex digits) of the autotuner's two candidate tables as written in the sources,
+    comments and white space removed."""
+    import hashlib
+    import re
+
+    h = hashlib.sha256()
+    csrc = os.path.join(ROOT, "ddp_classification_pytorch_amd", "csrc")
+    for fname, table in (("conv_igemm.hip", "kTgCfgs[] = {"), ("bindings.cpp", "kWgCfgs[] = {")):
+        with open(os.path.join(csrc, fname)) as f:
+            text = f.read()
+        i = text.index(table)
+        body = re.sub(r"//[^\n]*", "", text[i:text.index("};", i)])
+        h.update("".join(body.split()).encode())
+    return h.hexdigest()[:16]
+
+
+def load_dump_tuning(kops):
+    """Replay DUMP_TUNE_CACHE; returns the number of entries accepted."""
+    if not os.path.exists(DUMP_TUNE_CACHE):
+        raise SystemExit(f"bench.py: --dump-outputs needs {DUMP_TUNE_CACHE}")
+    with open(DUMP_TUNE_CACHE) as f:
+        first = f.readline().split()
+    want = ["#", "candidate", "tables", candidate_tables_fingerprint()]
+    if first != want:
+        raise SystemExit(f"bench.py: {DUMP_TUNE_CACHE} was recorded for other autotuner candidate tables "
+                         f"(its first line is {' '.join(first)!r}, the sources give {' '.join(want)!r}): record it again")
+    return tuning.load_cache(kops, DUMP_TUNE_CACHE)
+
+
+DUMP_MAX_ELEMS = 4 * 2**20  # per array: 16 MB of float32, all arrays together stay well under 64 MB
+
+
+def _dump_state(model):
+    """The tensors a step updates in place: parameters and BN running statistics."""
+    params = [p for _, p in model.named_parameters()]
+    stats = [b for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var"))]
+    return params, stats
+
+
+class StartState:
+    """The seeded state the run starts from (parameters, BN running statistics; momentum buffers
+    start at zero, which steps exactly as torch's first-gradient initialisation at dampening 0).
+    ``restore()`` puts it back in place, so the next step computes from the seeded inputs alone:
+    25 steps at lr 0.1 from random weights amplify last-bit differences to 11 % (relative L2, one
+    pair of runs) in the parameters between two runs of one build.  The price: the dumped step is
+    a first step, so nothing that shows only after an update (momentum accumulation) is in it."""
+
+    def __init__(self, model, opt):
+        self.opt = opt
+        self.params, self.stats = _dump_state(model)
+        with torch.no_grad():
+            self.saved = [t.detach().clone() for t in self.params + self.stats]
+
+    def restore(self):
+        with torch.no_grad():
+            torch._foreach_copy_([t.detach() for t in self.params + self.stats], self.saved)
+            bufs = [self.opt.state[p]["momentum_buffer"] for p in self.params
+                    if "momentum_buffer" in self.opt.state.get(p, {})]
+            if bufs:
+                torch._foreach_zero_(bufs)
+        Fn.bump_weight_generation()  # eager steps: the cached bf16 weight copies are stale
+
+
+def dump_outputs(path, loss, model):
+    """What the last timed step handed back, as ``path/<name>.npy`` (float32): the loss it returned
+    and the state it left in the model -- the gradients, the parameters after the optimizer step
+    and the BN running statistics -- each flattened and concatenated in ``named_parameters()`` /
+    ``named_buffers()`` order.  An array longer than DUMP_MAX_ELEMS is sampled at sorted indices
+    drawn once from a fixed seed, so two builds dump the same elements.  That step starts from
+    :class:`StartState`, so the arrays are a function of the seeded inputs and initial weights
+    only, whatever --steps and --warmup are."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+
+    def flat(tensors):
+        v = torch.cat([t.detach().reshape(-1).float() for t in tensors])
+        if v.numel() > DUMP_MAX_ELEMS:
+            gen = torch.Generator().manual_seed(20240229)
+            idx = torch.randint(0, v.numel(), (DUMP_MAX_ELEMS,), generator=gen).sort().values
+            v = v[idx.to(v.device)]
+        return v.cpu().numpy()
+
+    params, stats = _dump_state(model)
+    arrays = {"loss": loss.detach().reshape(-1).float().cpu().numpy(), "params": flat(params),
+              "grads": flat([p.grad for p in params if p.grad is not None])}
+    if stats:
+        arrays["bn_running_stats"] = flat(stats)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr.astype(np.float32, copy=False))
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     a = parse(argv)
@@ -248,6 +375,9 @@ def main(argv=None):
     kops.set_tuning(tuning.slot("autotune"), 1 if autotune else 0)
     # A/B experiments only: DCP_TUNE="name=value,..." sets kernel-config overrides (csrc/tune.h)
     tuning.apply(kops, os.environ.get("DCP_TUNE", ""))
+    if a.dump_outputs and autotune and not os.environ.get("DCP_TUNE_CACHE"):
+        load_dump_tuning(kops)
+    replayed = int(kops.autotune_entries())  # decisions known before the first step (either cache)
 
     torch.manual_seed(1234 + rank)
     model = build_bench_model(a).to(dev)
@@ -265,6 +395,7 @@ def main(argv=None):
     # bucket engine: the SGD kernel runs per gradient bucket right behind its all-reduce (its
     # step() after backward is then a no-op); torch DDP / one GPU: one launch after backward
     pddp.attach_optimizer(model, opt)
+    start = StartState(model, opt) if a.dump_outputs else None
 
     B, S = a.batch, a.image_size
     g = torch.Generator(device=dev)
@@ -327,13 +458,32 @@ def main(argv=None):
         prof = torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CPU,
                                                   torch.profiler.ProfilerActivity.CUDA])
         prof.__enter__()
-    dt, loss = timed(a.steps)
+    if start is None:
+        dt, loss = timed(a.steps)
+    else:
+        # --dump-outputs: the last of the timed steps starts again from the seeded state (put back
+        # between two timed stretches, outside both), so what it computes can be compared run to run
+        dt = timed(a.steps - 1)[0] if a.steps > 1 else 0.0
+        start.restore()
+        dt1, loss = timed(1)
+        dt += dt1
     if prof is not None:
         prof.__exit__(None, None, None)
         os.makedirs(a.profile_dir, exist_ok=True)
         with open(os.path.join(a.profile_dir, "bench_profile.txt"), "w") as f:
             f.write(prof.key_averages().table(sort_by="cuda_time_total", row_limit=60))
     dt, per_rank = gather_max(dt)
+    dump_tuning = None
+    if a.dump_outputs:
+        # shapes tuned by timing in this process: their kernels may differ in another run
+        dump_tuning = {"replayed": replayed, "timed": int(kops.autotune_entries()) - replayed}
+        if rank == 0:
+            dump_outputs(a.dump_outputs, loss, model)
+            sys.stderr.write(f"bench.py: --dump-outputs replayed {replayed} recorded autotuner decisions\n")
+            if dump_tuning["timed"]:
+                sys.stderr.write(f"bench.py: warning: {dump_tuning['timed']} shapes were not among them and were "
+                                 "tuned by timing; another run may pick other kernels for them and dump other "
+                                 "last bits (--no-autotune or DCP_TUNE_CACHE=<file> make it repeatable)\n")
     loss_v = float(loss.item())
     ms = dt / a.steps * 1000.0
     ips = B * world * a.steps / dt
@@ -370,6 +520,7 @@ def main(argv=None):
             "parallelism": f"dp{world}",
             "hip_graph": bool(a.graph),
             "autotune": bool(autotune),
+            "dump_tuning": dump_tuning,
             "syncbn": bool(a.syncbn),
             "grad_comm": a.grad_comm,
             "ddp_engine": a.ddp_engine if dist_on else None,
@@ -380,8 +531,8 @@ def main(argv=None):
             "max_mem_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1),
         },
     }
-    # The headline is measured.  What follows (bucket telemetry, the SyncBN phase, the collective
-    # probe) is diagnostic and must never cost the line: each phase is guarded, and a deadline
+    # The headline is measured.  What follows under --full (bucket telemetry, the SyncBN phases, the
+    # collective probe) is diagnostic and must never cost the line: each phase is guarded, and a deadline
     # watchdog prints the line and ends the rank if a phase hangs (e.g. one rank failed inside a
     # collective sequence the others are still in).
     emitted = threading.Event()
@@ -403,7 +554,8 @@ def main(argv=None):
         os._exit(0)
 
     extra_deadline = float(os.environ.get("DCP_BENCH_EXTRA_DEADLINE", "240"))
-    timer = threading.Timer(extra_deadline, watchdog) if dist_on else None
+    diag = dist_on and a.full  # a plain run ends with the headline
+    timer = threading.Timer(extra_deadline, watchdog) if diag else None
     if timer is not None:
         timer.daemon = True
         timer.start()
@@ -544,15 +696,15 @@ def main(argv=None):
         out["comm_probe"] = comm_probe(dev, world, bn_group)
 
     go = True
-    if dist_on and a.ddp_engine == "dcp" and a.telemetry_steps > 0:
+    if diag and a.ddp_engine == "dcp" and a.telemetry_steps > 0:
         go = guarded("telemetry", telemetry_phase)
-    elif dist_on:
+    elif diag:
         out["comm"] = {"engine": a.ddp_engine, "bucket_mb": [round(v, 2) for v in pddp.bucket_layout_mb(model)]}
-    if go and dist_on and not a.syncbn and a.syncbn_phase:
+    if go and diag and not a.syncbn and a.syncbn_phase:
         go = guarded("syncbn", syncbn_phase)
         if go and a.syncbn_peer:
             go = guarded("syncbn_peer", syncbn_peer_phase)
-    if go and dist_on and a.comm_probe and dist.get_backend() == "nccl":
+    if go and diag and a.comm_probe and dist.get_backend() == "nccl":
         go = guarded("probe", probe_phase)
     if timer is not None:
         timer.cancel()

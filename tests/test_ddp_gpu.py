@@ -2,7 +2,7 @@
 driver runs the real 1/2/4/8-GPU RCCL benchmark; RCCL refuses two ranks on one
 device, so these tests use gloo for the collectives while every op runs on cuda:0):
 
-* ``bench.py --gpus 2`` (self-launched ranks, no torchrun on the command line) prints one JSON
+* ``bench.py --gpus 2 --full`` (self-launched ranks, no torchrun on the command line) prints one JSON
   line with n_gpus == 2 and the SyncBN phase's number;
 * RCCL itself: a world_size-1 ``nccl`` process group (eager communicator init) under a forced
   DDP wrapper, one ResNet-18 training step whose gradients pass through the RCCL Reducer;
@@ -36,7 +36,7 @@ def test_bench_two_ranks_one_gpu():
     env = dict(os.environ, DCP_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--image-size", "64"]
+           "--batch", "8", "--image-size", "64", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -53,7 +53,7 @@ def test_bench_two_ranks_one_gpu():
 
 @pytest.mark.parametrize("graph", [False, True])
 def test_bench_force_ddp_rccl_world1(graph):
-    """bench.py --force-ddp: a world-1 RCCL group through the bucket engine, eager and HIP-graph
+    """bench.py --force-ddp --full: a world-1 RCCL group through the bucket engine, eager and HIP-graph
     replay, with the SyncBN phase, the bucket telemetry (eager) and the collective probe in the
     JSON line."""
     # DCP_SYNCBN_WORLD1: keep the SyncBN collectives at world 1 (torch -- and so the default -- skips them)
@@ -62,7 +62,7 @@ def test_bench_force_ddp_rccl_world1(graph):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--force-ddp", "--steps", "3", "--warmup", "2",
-           "--batch", "8", "--image-size", "64"] + (["--graph"] if graph else [])
+           "--batch", "8", "--image-size", "64", "--full"] + (["--graph"] if graph else [])
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -400,7 +400,7 @@ def test_bench_diagnostic_phase_failure_keeps_headline(inject):
                DCP_BENCH_EXTRA_DEADLINE="40")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--image-size", "64"]
+           "--batch", "8", "--image-size", "64", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]

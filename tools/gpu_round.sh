@@ -48,23 +48,23 @@ for step in "$@"; do
       tail -2 $O/gpu_tests.log ;;
     probe)
       # world-1 RCCL DDP step with the collective probe in its JSON (comm_probe)
-      timeout -k 10 300 python -u bench.py --force-ddp --steps 20 --warmup 5 > $O/ddp1_probe.log 2>&1
+      timeout -k 10 300 python -u bench.py --full --force-ddp --steps 20 --warmup 5 > $O/ddp1_probe.log 2>&1
       tail -1 $O/ddp1_probe.log | grep -o '"comm_probe": {[^}]*}[^}]*}[^}]*}' ;;
     ddp1)
-      timeout -k 10 300 python -u bench.py --force-ddp --batch 32 --graph --steps 100 --warmup 5 > $O/ddp1_b32g.log 2>&1
+      timeout -k 10 300 python -u bench.py --full --force-ddp --batch 32 --graph --steps 100 --warmup 5 > $O/ddp1_b32g.log 2>&1
       tail -1 $O/ddp1_b32g.log
-      timeout -k 10 300 python -u bench.py --force-ddp --batch 32 --steps 100 --warmup 5 > $O/ddp1_b32.log 2>&1
+      timeout -k 10 300 python -u bench.py --full --force-ddp --batch 32 --steps 100 --warmup 5 > $O/ddp1_b32.log 2>&1
       tail -1 $O/ddp1_b32.log
-      timeout -k 10 300 python -u bench.py --force-ddp --steps 20 --warmup 5 > $O/ddp1_b1024.log 2>&1
+      timeout -k 10 300 python -u bench.py --full --force-ddp --steps 20 --warmup 5 > $O/ddp1_b1024.log 2>&1
       tail -1 $O/ddp1_b1024.log
-      timeout -k 10 300 python -u bench.py --force-ddp --batch 128 --grad-comm bf16 --steps 30 --warmup 5 > $O/ddp1_b128bf16.log 2>&1
+      timeout -k 10 300 python -u bench.py --full --force-ddp --batch 128 --grad-comm bf16 --steps 30 --warmup 5 > $O/ddp1_b128bf16.log 2>&1
       tail -1 $O/ddp1_b128bf16.log ;;
     refcfg)
       # the reference's own configurations (BASELINE/main.py:29-30,148; ARCFACE/arc_main.py:38,69-73,
       # arc_train_hpc.sh:3): small per-GPU batches, HIP graph and eager, local BN and world-1 RCCL SyncBN
       run_ref() {  # tag, bench args...
         local t=$1; shift
-        timeout -k 10 300 python -u bench.py --steps 30 --warmup 5 "$@" > $O/ref_$t.log 2>&1
+        timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 5 "$@" > $O/ref_$t.log 2>&1
         # (the JSON line is the last one starting with "{": a world-1 DDP run may print after it)
         echo "$t $(grep '^{' $O/ref_$t.log | tail -1 | python -c 'import json,sys; r=json.loads(sys.stdin.read()); print(r["value"], r["ms_per_step"], r.get("syncbn_value"), r.get("syncbn_ms_per_step"))')"
       }
@@ -119,7 +119,7 @@ for step in "$@"; do
         tail -1 $O/bench_$c.log
       done ;;
     gloo2)
-      DCP_DIST_BACKEND=gloo timeout -k 10 300 python -u bench.py --gpus 2 --batch 256 --steps 5 --warmup 2 \
+      DCP_DIST_BACKEND=gloo timeout -k 10 300 python -u bench.py --full --gpus 2 --batch 256 --steps 5 --warmup 2 \
         > $O/bench_gloo2.log 2>&1
       tail -1 $O/bench_gloo2.log ;;
     prof)
