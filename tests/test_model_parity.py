@@ -7,6 +7,7 @@ import torch
 
 from ddp_classification_pytorch_amd.models import build_model
 from ddp_classification_pytorch_amd.ops import functional as Fn
+from tests.model_mirror import frozen_copy as _frozen_copy  # noqa: F401  (shared with test_block_grads)
 from tests.model_mirror import mirror_forward
 
 
@@ -104,25 +105,6 @@ def test_gpu_training_reduces_loss_like_mirror():
         o2.step()
     assert h1[-1] < 0.5 * h1[0], h1
     assert abs(h1[-1] - h2[-1]) < 0.25 * max(h2[-1], 0.2), (h1, h2)
-
-
-def _frozen_copy(m, seed=3):
-    """Non-trivial running statistics / affine, BN frozen (NESTED freeze_bn: eval + no affine grad)."""
-    from ddp_classification_pytorch_amd.models.layers import BatchNorm2d
-
-    g = torch.Generator().manual_seed(seed)
-    for mod in m.modules():
-        if isinstance(mod, BatchNorm2d):
-            C = mod.num_features
-            with torch.no_grad():
-                mod.running_mean.copy_(torch.randn(C, generator=g) * 0.1)
-                mod.running_var.copy_(torch.rand(C, generator=g) * 0.5 + 0.75)
-                mod.weight.copy_(torch.rand(C, generator=g) * 0.5 + 0.5)
-                mod.bias.copy_(torch.randn(C, generator=g) * 0.1)
-            mod.eval()
-            mod.weight.requires_grad_(False)
-            mod.bias.requires_grad_(False)
-    return m
 
 
 def _run_frozen(model, imgs, labels, ours):
