@@ -738,6 +738,97 @@ Tensor conv_wgrad(const Tensor& dy, const Tensor& x, int64_t KH, int64_t KW, int
   return dw;
 }
 
+// 1x1 stride-1 GEMM over one or two K-concatenated sources: out[p][co] = sum_c x[p][c] w[co][c] +
+// sum_k x2[p][k] w[co][C + k] (+ bias[co], added in fp32 before the bf16 rounding).  w: [Co, C (+ C2)] bf16.
+Tensor conv1x1_cat(const Tensor& x, const optional<Tensor>& x2, const Tensor& w, const optional<Tensor>& bias) {
+  CHECK_ACT(x);
+  CHECK_ACT(w);
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 2, "conv1x1_cat expects NHWC input and a [Co, K] weight");
+  const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3), Co = w.size(0);
+  int C2 = 0;
+  if (x2.has_value()) {
+    CHECK_ACT(*x2);
+    TORCH_CHECK(x2->dim() == 4 && x2->size(0) == N && x2->size(1) == H && x2->size(2) == W, "conv1x1_cat: x2 grid");
+    C2 = x2->size(3);
+    TORCH_CHECK(C2 % 64 == 0 && C2 > 0, "conv1x1_cat: the second source needs a multiple of 64 channels");
+  }
+  TORCH_CHECK(w.size(1) == C + C2, "conv1x1_cat: weight columns");
+  TORCH_CHECK(C % 64 == 0 && Co % 8 == 0, "conv1x1_cat channel layout");
+  TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv1x1_cat: too many pixels");
+  const float* bptr = nullptr;
+  if (bias.has_value()) {
+    CHECK_DEV(*bias);
+    CHECK_CONTIG(*bias);
+    CHECK_F32(*bias);
+    TORCH_CHECK(x2.has_value() && bias->numel() == Co, "conv1x1_cat: bias is [Co], with a second source");
+    bptr = bias->data_ptr<float>();
+  }
+  auto out = at::empty({N, H, W, Co}, bf16_like(x));
+  dcp::TapList t;
+  t.n = 1;
+  t.dy[0] = t.dx[0] = t.widx[0] = 0;
+  // (one source: the [Co][C] weight as a one-tap matrix; two: launch_tap_gemm's ldw = C + C2)
+  dcp::launch_tap_gemm(bp(x), N, H, W, C, bp(w), Co, 1, bpm(out), H, W, H, W, 1, 1, 0, 0, t, nullptr, nullptr, 0,
+                       zero_page(x.get_device()), cur_stream(), nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                       x2.has_value() ? bp(*x2) : nullptr, C2, bptr);
+  return out;
+}
+
+// Backward of conv3 (1x1 stride 1, a2 [N,H,W,m] -> C channels) and the training-mode BN behind it in one op,
+// from the masked gradient g of the BN's output and its sums [2,C] = (sum g, sum g xhat) (bn_lin.hip):
+// the BN's input gradient is never formed.  w3: [C,1,1,m] bf16, wt: [m,1,1,C] bf16 (its transpose).
+// Returns (d_a2 [N,H,W,m] bf16, dW3 [C,1,1,m] fp32); either may be skipped (an empty tensor).
+std::tuple<Tensor, Tensor> conv1x1_bn_lin_bwd(const Tensor& g, const Tensor& a2, const Tensor& w3, const Tensor& wt,
+                                              const Tensor& scale, const Tensor& invstd, const Tensor& sums,
+                                              double count, bool need_dx, bool need_dw) {
+  CHECK_ACT(g);
+  CHECK_ACT(a2);
+  CHECK_ACT(w3);
+  CHECK_ACT(wt);
+  TORCH_CHECK(g.dim() == 4 && a2.dim() == 4, "conv1x1_bn_lin_bwd expects NHWC tensors");
+  const int N = g.size(0), H = g.size(1), W = g.size(2), C = g.size(3), m = a2.size(3);
+  TORCH_CHECK(a2.size(0) == N && a2.size(1) == H && a2.size(2) == W, "conv1x1_bn_lin_bwd: a2 grid");
+  TORCH_CHECK(dcp::bn_lin_supported(m, C), "conv1x1_bn_lin_bwd: channels must be multiples of 64");
+  TORCH_CHECK(w3.numel() == (int64_t)C * m && w3.size(0) == C && wt.numel() == (int64_t)C * m && wt.size(0) == m,
+              "conv1x1_bn_lin_bwd: weight shapes");
+  for (const Tensor* t : {&scale, &invstd}) {
+    CHECK_DEV(*t);
+    CHECK_CONTIG(*t);
+    CHECK_F32(*t);
+    TORCH_CHECK(t->numel() == C, "conv1x1_bn_lin_bwd: per-channel vector size");
+  }
+  CHECK_DEV(sums);
+  CHECK_CONTIG(sums);
+  CHECK_F32(sums);
+  TORCH_CHECK(sums.numel() == 2 * (int64_t)C && count > 0, "conv1x1_bn_lin_bwd: sums [2,C]");
+  const float inv_count = (float)(1.0 / count);
+  auto st = cur_stream();
+  const int M = N * H * W;
+  TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv1x1_bn_lin_bwd: too many pixels");
+  auto cs = at::empty({m}, f32_like(g));
+  {
+    auto part = at::empty({dcp::bn_lin_colsum_partials(M, m), m}, f32_like(g));
+    dcp::launch_bn_lin_colsum(bp(a2), M, m, part.data_ptr<float>(), cs.data_ptr<float>(), st);
+  }
+  auto coef = at::empty({3, C}, f32_like(g));
+  auto qpart = at::empty({dcp::bn_lin_q_slices(m, C), m, m}, f32_like(g));
+  auto wcat = at::empty({m, C + m}, bf16_like(g));
+  auto bias = at::empty({m}, f32_like(g));
+  dcp::launch_bn_lin_prep(bp(w3), bp(wt), scale.data_ptr<float>(), invstd.data_ptr<float>(), sums.data_ptr<float>(),
+                          cs.data_ptr<float>(), inv_count, m, C, coef.data_ptr<float>(), qpart.data_ptr<float>(),
+                          bpm(wcat), bias.data_ptr<float>(), st);
+  Tensor dx = at::empty({0}, bf16_like(g)), dw = at::empty({0}, f32_like(g));
+  if (need_dx) dx = conv1x1_cat(g, a2, wcat, bias);
+  if (need_dw) {
+    const Tensor G = conv_wgrad(g, a2, 1, 1, 1, 0);    // [C,1,1,m]
+    const Tensor A2 = conv_wgrad(a2, a2, 1, 1, 1, 0);  // [m,1,1,m]
+    dw = at::empty({C, 1, 1, m}, f32_like(g));
+    dcp::launch_bn_lin_dw(G.data_ptr<float>(), A2.data_ptr<float>(), bp(w3), coef.data_ptr<float>(),
+                          cs.data_ptr<float>(), inv_count, m, C, dw.data_ptr<float>(), st);
+  }
+  return {dx, dw};
+}
+
 // weight gradient for conv_fwd_geo's geometry (output grid taken from dy)
 Tensor conv_wgrad_geo(const Tensor& dy, const Tensor& x, int64_t KH, int64_t KW, int64_t stride, int64_t pad) {
   CHECK_ACT(dy);
@@ -2013,6 +2104,11 @@ TORCH_LIBRARY(dcp, m) {
         &grouped_conv_wgrad);
   m.def("bn_stats(Tensor x, Tensor? slabs) -> Tensor", &bn_stats);
   m.def("colsum(Tensor x) -> Tensor", &colsum);
+  m.def("conv1x1_cat(Tensor x, Tensor? x2, Tensor w, Tensor? bias) -> Tensor", &conv1x1_cat);
+  m.def(
+      "conv1x1_bn_lin_bwd(Tensor g, Tensor a2, Tensor w3, Tensor wt, Tensor scale, Tensor invstd, Tensor sums, "
+      "float count, bool need_dx, bool need_dw) -> (Tensor, Tensor)",
+      &conv1x1_bn_lin_bwd);
   m.def(
       "bn_stats_finalize(Tensor x, Tensor? slabs, Tensor? gamma, Tensor? beta, Tensor? run_mean, Tensor? run_var, "
       "float momentum, float eps, float iabn_eps=-1., Tensor(a!)? rgamma_out=None) -> (Tensor, Tensor, Tensor, Tensor)",

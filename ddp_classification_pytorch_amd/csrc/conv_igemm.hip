@@ -104,6 +104,13 @@ struct TapGemmParams {
   // slices are cut in 64-deep k units (k64 of them), so every tile width / k depth sums the same slices
   f32x4* kp;
   int ksplit, kmode, k64;
+  // S2 instantiations (EPI 0, FAST): a second A source concatenated along K.  k-tiles nkt1 .. nkt-1 read
+  // src2 [pixels][Cs2] (a 1x1 source on src's pixel grid: the pixel of tap offset (0, 0)) against the weight
+  // columns woff2 .. woff2 + Cs2 of the one [Co][ldw] matrix.  bias2 (optional, fp32 [Co]) is added to the
+  // accumulators before their one bf16 rounding.
+  const bf16* src2;
+  const float* bias2;
+  int Cs2, nkt1, woff2;
 };
 
 __device__ __forceinline__ int tap_dy(int v) { return (int)(int8_t)(v & 0xff); }
@@ -347,10 +354,11 @@ __device__ __forceinline__ void tg_image_store(const TapGemmParams& p, char* E, 
 // the raw s_barrier, drained by a counted vmcnt -- for deep-K shapes at one block per CU.
 // three waves per SIMD: the fused BN-backward epilogue otherwise lands one register past the
 // 168-register step and halves to two workgroups per CU
-template <int BN, int EPI, bool FAST, int NS = 2, int BK = 64, bool PRO = false, bool KS = false>
+template <int BN, int EPI, bool FAST, int NS = 2, int BK = 64, bool PRO = false, bool KS = false, bool S2 = false>
 __global__ void __launch_bounds__(256, 3)
 tap_gemm_kernel(const TapGemmParams p) {
   static_assert(NS == 2 || FAST, "the LDS ring needs the one-tap-per-k-tile path");
+  static_assert(!S2 || (FAST && EPI == 0 && !PRO && !KS), "the second A source: plain FAST store kernels only");
   static_assert(!PRO || (FAST && NS == 2 && EPI < 2), "the BN prologue: FAST double-buffered forward only");
   static_assert(BK == 64 || BK == 32, "k-tile depth");
   constexpr int BM = 128;                 // pixel rows per block
@@ -382,6 +390,7 @@ tap_gemm_kernel(const TapGemmParams p) {
   // vector-issue bound on this address arithmetic).  Rows past M / channels past Co read a
   // clamped valid row: their outputs are never stored nor counted in the statistics.
   const bf16* fa_ptr[AI];
+  const bf16* fa2_ptr[S2 ? AI : 1];
   uint32_t fa_vm[AI];
   const bf16* fb_ptr[BN / (4 * RPI)];
   if constexpr (FAST) {
@@ -396,6 +405,9 @@ tap_gemm_kernel(const TapGemmParams p) {
       const int ys = y * p.ss, xs = x * p.ss;
       fa_ptr[i] = p.src + ((size_t)n * p.Hs * p.Ws + (size_t)ys * p.Ws + xs) * p.Cs +
                   ((lane % CH) ^ swz_chunk<BK>(r)) * 8;
+      if constexpr (S2)
+        fa2_ptr[i] = p.src2 + ((size_t)n * p.Hs * p.Ws + (size_t)ys * p.Ws + xs) * p.Cs2 +
+                     ((lane % CH) ^ swz_chunk<BK>(r)) * 8;
       uint32_t vm = 0;
       for (int t = 0; t < p.ntaps; ++t) {
         const int tv = p.tap[t];
@@ -467,6 +479,16 @@ tap_gemm_kernel(const TapGemmParams p) {
   auto stage = [&](int kt, int buf) {
     char* As = smem + buf * STAGE;
     char* Bs = As + A_BYTES;
+    if constexpr (S2) {
+      if (kt >= p.nkt1) {  // (wave-uniform) the second source: every row valid, no taps
+        const long off2 = (long)(kt - p.nkt1) * BK;
+#pragma unroll
+        for (int i = 0; i < AI; ++i) dma16_tracked(fa2_ptr[i] + off2, As + (wave * AI + i) * 1024);
+#pragma unroll
+        for (int i = 0; i < BI; ++i) dma16_tracked(fb_ptr[i] + (p.woff2 + off2), Bs + (wave * BI + i) * 1024);
+        return;
+      }
+    }
     if constexpr (FAST) {
       const int t = kt / tiles_per_tap;
       const int cbase = (kt - t * tiles_per_tap) * BK;
@@ -741,6 +763,17 @@ tap_gemm_kernel(const TapGemmParams p) {
   }
 
   if constexpr (EPI != 2) {
+    if constexpr (S2) {
+      if (p.bias2 != nullptr) {  // fp32, before the epilogue's one bf16 rounding
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          const int co = n0 + wn * (BN / 2) + j * 16 + (lane >> 4) * 4;
+          const f32x4 b = co < p.Co ? *(const f32x4*)(p.bias2 + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[j][i] += b;
+        }
+      }
+    }
     tg_store_epilogue<BN, EPI>(p, acc, smem, m0, n0, tid, lane, wm, wn);
     return;
   }
@@ -795,9 +828,10 @@ tap_gemm_kernel(const TapGemmParams p) {
 // ---------------------------------------------------------------------------
 // (CFW: 16-channel accumulator fragments per wave; the 4-wave 256 x 256 tile at CFW = 8 measured
 // slower on every R50 shape, profiles/r4/big4_tile_ab_b1024.txt, and was removed)
-template <int WM, int WN, int NS, int EPI, int CFW = 4>
+template <int WM, int WN, int NS, int EPI, int CFW = 4, bool S2 = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2)
 tap_gemm_big_kernel(const TapGemmParams p) {
+  static_assert(!S2 || EPI == 0, "the second A source: plain store epilogue only");
   constexpr int NT = 64 * WM * WN, NW = WM * WN;
   constexpr int BM = 128 * WM, BN = 16 * CFW * WN, BK = 32;
   constexpr int ROWB = BK * 2, CH = BK / 8, RPI = 64 / CH;  // 64-byte rows, 16 rows per LDS-DMA
@@ -819,6 +853,7 @@ tap_gemm_big_kernel(const TapGemmParams p) {
   // per-slot source pointers + tap-validity masks (as tap_gemm_kernel's FAST path); rows past M
   // and channels past Co read a clamped valid row and are never stored or counted
   const bf16* fa_ptr[AI];
+  const bf16* fa2_ptr[S2 ? AI : 1];
   uint32_t fa_vm[AI];
   const bf16* fb_ptr[BI];
 #pragma unroll
@@ -831,6 +866,8 @@ tap_gemm_big_kernel(const TapGemmParams p) {
     const uint32_t y = q - n * p.Hy;
     const int ys = y * p.ss, xs = x * p.ss;
     fa_ptr[i] = p.src + ((size_t)n * p.Hs * p.Ws + (size_t)ys * p.Ws + xs) * p.Cs + ((lane % CH) ^ swz_chunk<BK>(r)) * 8;
+    if constexpr (S2)
+      fa2_ptr[i] = p.src2 + ((size_t)n * p.Hs * p.Ws + (size_t)ys * p.Ws + xs) * p.Cs2 + ((lane % CH) ^ swz_chunk<BK>(r)) * 8;
     uint32_t vm = 0;
     for (int t = 0; t < p.ntaps; ++t) {
       const int tv = p.tap[t];
@@ -845,9 +882,25 @@ tap_gemm_big_kernel(const TapGemmParams p) {
     fb_ptr[i] = p.wt + (size_t)min(n0 + r, p.Co - 1) * p.ldw + ((lane % CH) ^ swz_chunk<BK>(r)) * 8;
   }
   const int tiles_per_tap = p.cpt / CH;
+  // S2: k-tile kt2 >= 0 of the second source (every row valid, no taps), wave-uniform
+  auto stage2 = [&](int kt2, char* As, char* Bs) {
+    if constexpr (S2) {
+      const long off2 = (long)kt2 * BK;
+#pragma unroll
+      for (int i = 0; i < AI; ++i) dma16_tracked(fa2_ptr[i] + off2, As + (wave * AI + i) * 1024);
+#pragma unroll
+      for (int i = 0; i < BI; ++i) dma16_tracked(fb_ptr[i] + (p.woff2 + off2), Bs + (wave * BI + i) * 1024);
+    }
+  };
   auto stage = [&](int kt, int slot) {
     char* As = smem + slot * STAGE;
     char* Bs = As + A_BYTES;
+    if constexpr (S2) {
+      if (kt >= p.nkt1) {
+        stage2(kt - p.nkt1, As, Bs);
+        return;
+      }
+    }
     const int t = kt / tiles_per_tap;
     const int cbase = (kt - t * tiles_per_tap) * BK;
     const int tv = p.tap[t];
@@ -931,9 +984,17 @@ tap_gemm_big_kernel(const TapGemmParams p) {
     // fragment reads too -- before every DMA.
     const int tap_lane = lane < p.ntaps ? p.tap[lane] : 0;
     int st_t = (NS - 1) / tiles_per_tap, st_c = ((NS - 1) - st_t * tiles_per_tap) * BK;
+    int st_k2 = (NS - 1) - p.nkt1;  // S2: the next k-tile to stage, counted from the second source's first
     auto stage_next = [&](int slot) {
       char* As = smem + slot * STAGE;
       char* Bs = As + A_BYTES;
+      if constexpr (S2) {
+        const int k2 = st_k2++;
+        if (k2 >= 0) {
+          stage2(k2, As, Bs);
+          return;
+        }
+      }
       const int tv = __builtin_amdgcn_readlane(tap_lane, st_t);
       const long aoff = (long)(tap_dy(tv) * p.Ws + tap_dx(tv)) * p.Cs + st_c;  // wave-uniform
       const long boff = (long)tap_w(tv) * p.Cs + st_c;
@@ -1015,6 +1076,17 @@ tap_gemm_big_kernel(const TapGemmParams p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (p.ablate & 4) return;  // timing ablation: no epilogue
+  if constexpr (S2) {
+    if (p.bias2 != nullptr) {  // fp32, before the epilogue's one bf16 rounding
+#pragma unroll
+      for (int j = 0; j < CFW; ++j) {
+        const int co = n0 + wn * (16 * CFW) + j * 16 + (lane >> 4) * 4;
+        const f32x4 b = co < p.Co ? *(const f32x4*)(p.bias2 + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[j][i] += b;
+      }
+    }
+  }
 
   // ---- epilogue: quadrant (h, qc) = pixels h*128.., channels qc*128.. at smem + (h*QN + qc) * 32 KB ----
   {
@@ -1049,9 +1121,10 @@ tap_gemm_big_kernel(const TapGemmParams p) {
 // lanes, and every attempt to fold the one-tile kernel above into it (opaque per-tile parameter
 // pointers, laundered lane index) either spilled or copied the parameters to scratch and ran the
 // big tile 2.5x slower (d4d972e: 512-channel 7x7 3x3 220 -> 645 us).
-template <int WM, int WN, int NS, int EPI, int CFW = 4>
+template <int WM, int WN, int NS, int EPI, int CFW = 4, bool S2 = false>
 __global__ void __launch_bounds__(64 * WM * WN, 2)
 tap_gemm_big_loop_kernel(const TapGemmParams p0) {
+  static_assert(!S2 || EPI == 0, "the second A source: plain store epilogue only");
   constexpr int NT = 64 * WM * WN, NW = WM * WN;
   constexpr int BM = 128 * WM, BN = 16 * CFW * WN, BK = 32;
   constexpr int ROWB = BK * 2, CH = BK / 8, RPI = 64 / CH;  // 64-byte rows, 16 rows per LDS-DMA
@@ -1124,6 +1197,8 @@ tap_gemm_big_loop_kernel(const TapGemmParams p0) {
     int kWs = p.Ws, kCs = p.Cs, kabl = p.ablate;
     const bf16* kzero = p.zero;
     asm volatile("" : "+s"(kWs), "+s"(kCs), "+s"(kabl), "+s"(kzero));
+    int kn1 = S2 ? p.nkt1 : 0, kw2 = S2 ? p.woff2 : 0;  // (S2: the second source's first k-tile / weight column)
+    if constexpr (S2) asm volatile("" : "+s"(kn1), "+s"(kw2));
     // the lane index likewise: every lane-derived LDS / global offset is recomputed per tile
     // instead of being hoisted and held in VGPRs through the k-loop
     int tid = threadIdx.x;
@@ -1139,6 +1214,7 @@ tap_gemm_big_loop_kernel(const TapGemmParams p0) {
     // per-slot source pointers + tap-validity masks (as tap_gemm_kernel's FAST path); rows past M
     // and channels past Co read a clamped valid row and are never stored or counted
     const bf16* fa_ptr[AI];
+    const bf16* fa2_ptr[S2 ? AI : 1];
     uint32_t fa_vm[AI];
     const bf16* fb_ptr[BI];
   #pragma unroll
@@ -1151,6 +1227,8 @@ tap_gemm_big_loop_kernel(const TapGemmParams p0) {
       const uint32_t y = q - n * p.Hy;
       const int ys = y * p.ss, xs = x * p.ss;
       fa_ptr[i] = p.src + ((size_t)n * p.Hs * p.Ws + (size_t)ys * p.Ws + xs) * p.Cs + ((lane % CH) ^ swz_chunk<BK>(r)) * 8;
+      if constexpr (S2)
+        fa2_ptr[i] = p.src2 + ((size_t)n * p.Hs * p.Ws + (size_t)ys * p.Ws + xs) * p.Cs2 + ((lane % CH) ^ swz_chunk<BK>(r)) * 8;
       uint32_t vm = 0;
       for (int t = 0; t < p.ntaps; ++t) {
         const int tv = pk->tap[t];
@@ -1170,6 +1248,16 @@ tap_gemm_big_loop_kernel(const TapGemmParams p0) {
       char* As = smem + slot * STAGE;
       char* Bs = As + A_BYTES;
       const int ka = kb + kt;
+      if constexpr (S2) {
+        if (ka >= kn1) {  // (wave-uniform) the second source: every row valid, no taps
+          const long off2 = (long)(ka - kn1) * BK;
+  #pragma unroll
+          for (int i = 0; i < AI; ++i) dma16_tracked(fa2_ptr[i] + off2, As + (wave * AI + i) * 1024);
+  #pragma unroll
+          for (int i = 0; i < BI; ++i) dma16_tracked(fb_ptr[i] + (kw2 + off2), Bs + (wave * BI + i) * 1024);
+          return;
+        }
+      }
       const int t = ka / tiles_per_tap;
       const int cbase = (ka - t * tiles_per_tap) * BK;
       const int tv = pk->tap[t];
@@ -1253,9 +1341,21 @@ tap_gemm_big_loop_kernel(const TapGemmParams p0) {
       // fragment reads too -- before every DMA.
       const int tap_lane = lane < p.ntaps ? pk->tap[lane] : 0;
       int st_t = (kb + NS - 1) / tiles_per_tap, st_c = ((kb + NS - 1) - st_t * tiles_per_tap) * BK;
+      int st_k2 = (kb + NS - 1) - kn1;  // S2: the next k-tile to stage, counted from the second source's first
       auto stage_next = [&](int slot) {
         char* As = smem + slot * STAGE;
         char* Bs = As + A_BYTES;
+        if constexpr (S2) {
+          const int k2 = st_k2++;
+          if (k2 >= 0) {
+            const long off2 = (long)k2 * BK;
+  #pragma unroll
+            for (int i = 0; i < AI; ++i) dma16_tracked(fa2_ptr[i] + off2, As + (wave * AI + i) * 1024);
+  #pragma unroll
+            for (int i = 0; i < BI; ++i) dma16_tracked(fb_ptr[i] + (kw2 + off2), Bs + (wave * BI + i) * 1024);
+            return;
+          }
+        }
         const int tv = __builtin_amdgcn_readlane(tap_lane, st_t);
         const long aoff = (long)(tap_dy(tv) * kWs + tap_dx(tv)) * kCs + st_c;  // wave-uniform
         const long boff = (long)tap_w(tv) * kCs + st_c;
@@ -1374,7 +1474,16 @@ tap_gemm_big_loop_kernel(const TapGemmParams p0) {
       skp = p.sk_ws + ((size_t)(blockIdx.x + 1) * NW + wave) * (CFW * 8 * 64) + lane;
     }
     if (p.ablate & 4) continue;  // timing ablation: no epilogue
-
+    // S2: the fp32 bias of this lane's channels, added before the one bf16 rounding (once per tile: by
+    // its finisher)
+    f32x4 b2[S2 ? CFW : 1];
+    if constexpr (S2) {
+  #pragma unroll
+      for (int j = 0; j < CFW; ++j) {
+        const int co = n0 + wn * (16 * CFW) + j * 16 + (lane >> 4) * 4;
+        b2[j] = (p.bias2 != nullptr && co < p.Co) ? *(const f32x4*)(p.bias2 + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
     // ---- epilogue: quadrant (h, qc) = pixels h*128.., channels qc*128.. at smem + (h*QN + qc) * 32 KB ----
     {
       char* Q = smem + (wm * QN + (wn * 16 * CFW) / 128) * 32768;
@@ -1387,6 +1496,7 @@ tap_gemm_big_loop_kernel(const TapGemmParams p0) {
           const uint32_t cl = cb + j * 16 + (lane >> 4) * 4;
           f32x4 a = acc[j][i];
           if (skp != nullptr) a += skp[(j * 8 + i) * 64];  // fp32 partial, before the one rounding
+          if constexpr (S2) a += b2[j];
           bf16x4 o;
   #pragma unroll
           for (int r = 0; r < 4; ++r) o[r] = f2bf(a[r]);
@@ -1917,9 +2027,10 @@ wgrad64_kernel(const WgradParams p) {
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
-template <int BN, int EPI, bool FAST, int NS, int BK = 64, bool PRO = false>
+template <int BN, int EPI, bool FAST, int NS, int BK = 64, bool PRO = false, bool S2 = false>
 static void launch_tg(TapGemmParams p, int grid, hipStream_t stream) {
-  p.nkt = (p.ntaps * p.cpt + BK / 8 - 1) / (BK / 8);
+  p.nkt1 = (p.ntaps * p.cpt + BK / 8 - 1) / (BK / 8);
+  p.nkt = p.nkt1 + (S2 ? p.Cs2 / BK : 0);  // (Cs2 % 64 == 0: whole k-tiles at either depth)
   // LDS: the stages the k-loop actually uses (short-K shapes -- 1x1 convs with 64 input
   // channels -- need one, which lets more workgroups share a CU) or the epilogue image
   const size_t stage = (size_t)(128 + BN) * BK * 2;
@@ -1936,9 +2047,9 @@ static void launch_tg(TapGemmParams p, int grid, hipStream_t stream) {
   if (full > 64 * 1024) {
     static bool attr = false;
     if (!attr) {
-      (void)hipFuncSetAttribute((const void*)tap_gemm_kernel<BN, EPI, FAST, NS, BK, PRO>,
+      (void)hipFuncSetAttribute((const void*)tap_gemm_kernel<BN, EPI, FAST, NS, BK, PRO, false, S2>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)full);
-      if constexpr (BN == 64 && FAST && !PRO && NS <= 3)
+      if constexpr (BN == 64 && FAST && !PRO && NS <= 3 && !S2)
         (void)hipFuncSetAttribute((const void*)tap_gemm_kernel<BN, EPI, FAST, NS, BK, PRO, true>,
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)full);
       attr = true;
@@ -1948,7 +2059,7 @@ static void launch_tg(TapGemmParams p, int grid, hipStream_t stream) {
   p.kp = nullptr;
   // split-K (tg_split_slices): the 64-channel FAST tiles with <= 3 stages, the configurations the
   // short grids it applies to run (the heuristic picks 64-channel tiles there)
-  if constexpr (BN == 64 && FAST && !PRO && NS <= 3) {
+  if constexpr (BN == 64 && FAST && !PRO && NS <= 3 && !S2) {
     if (p.ksplit > 1 && g_ws_alloc != nullptr) {
       const size_t bytes = (size_t)p.ksplit * grid * (BN / 32) * 4 * 256 * sizeof(f32x4);
       void* ws = g_ws_alloc(bytes, stream);
@@ -1964,7 +2075,7 @@ static void launch_tg(TapGemmParams p, int grid, hipStream_t stream) {
       }
     }
   }
-  hipLaunchKernelGGL((tap_gemm_kernel<BN, EPI, FAST, NS, BK, PRO>), dim3(grid), dim3(256), lds, stream, p);
+  hipLaunchKernelGGL((tap_gemm_kernel<BN, EPI, FAST, NS, BK, PRO, false, S2>), dim3(grid), dim3(256), lds, stream, p);
 }
 
 template <int WM, int WN, int NS, int CFW = 4>
@@ -2030,11 +2141,18 @@ static void launch_big(TapGemmParams p, int epi, hipStream_t stream) {
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipFuncSetAttribute((const void*)tap_gemm_big_loop_kernel<WM, WN, NS, 1, CFW>,
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipFuncSetAttribute((const void*)tap_gemm_big_kernel<WM, WN, NS, 0, CFW, true>,
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipFuncSetAttribute((const void*)tap_gemm_big_loop_kernel<WM, WN, NS, 0, CFW, true>,
+                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr = true;
   }
   const bool loop = p.persist || p.sk_ws != nullptr;
   const dim3 blk(64 * WM * WN);
-  if (epi == 1) {
+  if (p.src2 != nullptr) {  // (epi == 0: checked by the caller)
+    if (loop) hipLaunchKernelGGL((tap_gemm_big_loop_kernel<WM, WN, NS, 0, CFW, true>), dim3(grid), blk, lds, stream, p);
+    else hipLaunchKernelGGL((tap_gemm_big_kernel<WM, WN, NS, 0, CFW, true>), dim3(grid), blk, lds, stream, p);
+  } else if (epi == 1) {
     if (loop) hipLaunchKernelGGL((tap_gemm_big_loop_kernel<WM, WN, NS, 1, CFW>), dim3(grid), blk, lds, stream, p);
     else hipLaunchKernelGGL((tap_gemm_big_kernel<WM, WN, NS, 1, CFW>), dim3(grid), blk, lds, stream, p);
   } else {
@@ -2095,8 +2213,10 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
                           bf16* dst, int Hd, int Wd, int Hy, int Wy, int ss, int ds, int oy, int ox,
                           const TapList& taps, float* stats, const float* bias, int relu,
                           const bf16* zero, hipStream_t stream, const bf16* addsrc, const BnBwdEpi* bnb,
-                          const AffineEpi* aff, const float* pscale, const float* pshift, int nbias) {
+                          const AffineEpi* aff, const float* pscale, const float* pshift, int nbias,
+                          const bf16* src2, int Cs2, const float* bias2) {
   TapGemmParams p;
+  p.src2 = src2; p.bias2 = bias2; p.Cs2 = src2 ? Cs2 : 0; p.woff2 = T * Cs; p.nkt1 = 0;
   p.pscale = pscale;
   p.pshift = pshift;
   p.src = src; p.wt = wt; p.dst = dst; p.stats = stats; p.zero = zero; p.addsrc = addsrc;
@@ -2113,7 +2233,7 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   p.Hy = Hy; p.Wy = Wy; p.ss = ss;
   p.Hd = Hd; p.Wd = Wd; p.ds = ds; p.oy = oy; p.ox = ox;
   p.Co = Co; p.T = T; p.M = N * Hy * Wy;
-  p.ntaps = taps.n; p.cpt = Cs / 8; p.ldw = T * Cs;
+  p.ntaps = taps.n; p.cpt = Cs / 8; p.ldw = T * Cs + p.Cs2;
   p.nkt = (taps.n * p.cpt + 7) / 8;
   p.relu = relu; p.bias = bias; p.nbias = (nbias > 0 && nbias < Co) ? nbias : Co;
   p.div_wy = make_fastdiv(Wy); p.div_hy = make_fastdiv(Hy); p.div_cpt = make_fastdiv(p.cpt);
@@ -2130,6 +2250,11 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
     epi = bnb->mask != nullptr ? 4 : 3;
   }
   const bool fast = (p.cpt & 7) == 0 && taps.n <= 32;  // FAST: 32-bit tap-validity masks
+  if (src2 != nullptr && !(fast && epi == 0 && aff == nullptr && pscale == nullptr && Cs2 > 0 && Cs2 % 64 == 0 &&
+                           Co % 8 == 0 && taps.n >= 1)) {
+    fprintf(stderr, "launch_tap_gemm: the second source needs a plain FAST store GEMM and Cs2 %% 64 == 0\n");
+    abort();
+  }
   // config: BN (64/128 output channels per tile) and NS (LDS stages); g_tune overrides the
   // heuristic (tuning experiments only)
   const int env_bn = g_tune[kTgTileN], env_ns = g_tune[kTgStages];
@@ -2141,6 +2266,7 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   p.sk_ws = nullptr;
   p.sk_flags = nullptr;
   p.ksplit = tg_split_slices(p.M, Co, taps.n * Cs);  // (the 128-row kernels; tile widths 64 / 128 / 256)
+  if (src2 != nullptr) p.ksplit = 0;  // (the split instantiations have no second source)
   p.k64 = (taps.n * Cs + 63) / 64;
   p.kp = nullptr;
   p.kmode = 0;
@@ -2172,7 +2298,7 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   const bool plain1x1 = fast && (epi == 0 || epi == 1) && taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 &&
                         taps.widx[0] == 0 && ss == 1 && ds == 1 && oy == 0 && ox == 0 && Hd == Hy && Wd == Wy &&
                         Hs == Hy && Ws == Wy && T == 1 && addsrc == nullptr && aff == nullptr && bnb == nullptr &&
-                        pscale == nullptr && bias == nullptr && relu == 0;
+                        pscale == nullptr && bias == nullptr && relu == 0 && src2 == nullptr;
   if (g_tune[kTgWs] == 1 && plain1x1 && conv1x1_ws_supported(Cs, Co, p.M)) {
     if (p.ablate == 0 && launch_conv1x1_ws(src, wt, T * Cs, dst, stats, zero, p.M, Cs, Co, stream)) return;
   }
@@ -2187,7 +2313,8 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
                       Co >= 128;
   const int big = big_ok ? big_tile_pick(g_tune[kTgBig], p.M, Co, taps.n, ds) : 0;
   if (big != 0) {
-    p.nkt = taps.n * p.cpt / 4;  // 32-deep k-tiles (cpt % 8 == 0 on FAST shapes)
+    p.nkt1 = taps.n * p.cpt / 4;  // 32-deep k-tiles (cpt % 8 == 0 on FAST shapes)
+    p.nkt = p.nkt1 + p.Cs2 / 32;
     if (big == 1 && g_tune[kTgBigStages] == 5) launch_big<2, 4, 5>(p, epi, stream);
     else if (big == 1) launch_big<2, 4, 4>(p, epi, stream);
     else launch_big<2, 2, 3>(p, epi, stream);
@@ -2196,7 +2323,7 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   // 256-channel tiles (g_tune[kTgTileN] = 256, A/B and autotuner): each wave 64 rows x 128 channels, the
   // A tile read once per 256 output channels -- for the short-K expansion 1x1 convs, whose A reads
   // are half of their bytes at 128-channel tiles.  Plain / statistics epilogue only.
-  if (bn == 256 && !(fast && (epi == 0 || epi == 1) && pscale == nullptr && Co > 128)) bn = 128;
+  if (bn == 256 && !(fast && (epi == 0 || epi == 1) && pscale == nullptr && Co > 128 && src2 == nullptr)) bn = 128;
   if (bn == 256) {
     // (32-deep k-tiles only: the 64-deep variant spills at the 168-register cap)
     const int grid256 = ntm * ((Co + 255) / 256);
@@ -2223,6 +2350,18 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   }
     if (bn == 64) { DCP_TG_PRO(64) } else { DCP_TG_PRO(128) }
 #undef DCP_TG_PRO
+    return;
+  }
+  if (src2 != nullptr) {
+#define DCP_TG_S2(BN_)                                                                 \
+  if (bk32 && ns == 2) launch_tg<BN_, 0, true, 2, 32, false, true>(p, grid, stream);   \
+  else if (bk32 && ns == 3) launch_tg<BN_, 0, true, 3, 32, false, true>(p, grid, stream); \
+  else if (bk32 && ns == 4) launch_tg<BN_, 0, true, 4, 32, false, true>(p, grid, stream); \
+  else if (ns == 2) launch_tg<BN_, 0, true, 2, 64, false, true>(p, grid, stream);      \
+  else if (ns == 3) launch_tg<BN_, 0, true, 3, 64, false, true>(p, grid, stream);      \
+  else launch_tg<BN_, 0, true, 4, 64, false, true>(p, grid, stream);
+    if (bn == 64) { DCP_TG_S2(64) } else { DCP_TG_S2(128) }
+#undef DCP_TG_S2
     return;
   }
 #define DCP_TG_NS(BN_, EPI_, FAST_)                                                    \
@@ -2343,10 +2482,11 @@ void launch_tap_gemm(const bf16* src, int N, int Hs, int Ws, int Cs,
                      bf16* dst, int Hd, int Wd, int Hy, int Wy, int ss, int ds, int oy, int ox,
                      const TapList& taps, float* stats, const float* bias, int relu,
                      const bf16* zero, hipStream_t stream, const bf16* addsrc, const BnBwdEpi* bnb,
-                     const AffineEpi* aff, const float* pscale, const float* pshift, int nbias) {
+                     const AffineEpi* aff, const float* pscale, const float* pshift, int nbias,
+                     const bf16* src2, int Cs2, const float* bias2) {
   auto run = [&]() {
     tap_gemm_impl(src, N, Hs, Ws, Cs, wt, Co, T, dst, Hd, Wd, Hy, Wy, ss, ds, oy, ox, taps, stats, bias, relu, zero,
-                  stream, addsrc, bnb, aff, pscale, pshift, nbias);
+                  stream, addsrc, bnb, aff, pscale, pshift, nbias, src2, Cs2, bias2);
   };
   const bool fast = (Cs % 64) == 0 && taps.n <= 32;
   // only the FAST shapes have alternatives; A/B overrides set by hand win over the tuner
@@ -2362,6 +2502,10 @@ void launch_tap_gemm(const bf16* src, int N, int Hs, int Ws, int Cs,
                      addsrc != nullptr, bnb ? (bnb->mask ? 2 : 1) : 0, aff != nullptr);
   for (int i = 0; i < taps.n && len < (int)sizeof(kb) - 16; ++i)
     len += snprintf(kb + len, sizeof(kb) - len, "%d,%d,%d;", taps.dy[i], taps.dx[i], taps.widx[i]);
+  // a second source is a field of its own (single-source keys keep their form: earlier caches stay valid
+  // and can never match a two-source problem)
+  if (src2 != nullptr && len < (int)sizeof(kb) - 24)
+    len += snprintf(kb + len, sizeof(kb) - len, "|s2:%d,%d", Cs2, bias2 != nullptr);
   const std::string key(kb);
   int choice = -1;
   {
@@ -2382,7 +2526,7 @@ void launch_tap_gemm(const bf16* src, int N, int Hs, int Ws, int Cs,
     choice = 0;
     const bool big_ok = bnb == nullptr && aff == nullptr && bias == nullptr && relu == 0 && Co >= 128;
     // where the 128-row kernels split K, the (unsplit) big tiles would sum another way: not candidates
-    const bool ksplit = tg_split_slices(N * Hy * Wy, Co, taps.n * Cs) >= 2;
+    const bool ksplit = src2 == nullptr && tg_split_slices(N * Hy * Wy, Co, taps.n * Cs) >= 2;
     for (int c = 0; c < (int)(sizeof(kTgCfgs) / sizeof(kTgCfgs[0])); ++c) {
       const TgCfg& cfg = kTgCfgs[c];
       // (those that would not split: big tiles, 128 / 256-channel tiles, the 4-stage ring)
@@ -2391,8 +2535,9 @@ void launch_tap_gemm(const bf16* src, int N, int Hs, int Ws, int Cs,
         continue;
       if (cfg.big == 3 && !big_ok) continue;
       if (cfg.big == 1 && !(big_ok && Co >= 256)) continue;  // (the ping-pong candidate too)
-      if (cfg.bn == 256 && !(Co > 128 && bnb == nullptr && bias == nullptr && relu == 0)) continue;
+      if (cfg.bn == 256 && !(Co > 128 && bnb == nullptr && bias == nullptr && relu == 0 && src2 == nullptr)) continue;
       if (cfg.bn == 64 && Co <= 64 && cfg.ns == 0) continue;  // the heuristic's tile already
+      if ((cfg.ws == 1 || cfg.ps != 0) && src2 != nullptr) continue;  // (single-source kernels)
       if (cfg.ws == 1 && !(taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 && ss == 1 && ds == 1 && Hd == Hy &&
                            Wd == Wy && Hs == Hy && Ws == Wy && T == 1 && addsrc == nullptr && aff == nullptr &&
                            bnb == nullptr && bias == nullptr && relu == 0 &&

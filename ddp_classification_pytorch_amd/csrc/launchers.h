@@ -69,7 +69,11 @@ void launch_tap_gemm(const bf16* src, int N, int Hs, int Ws, int Cs, const bf16*
                      int Wd, int Hy, int Wy, int ss, int ds, int oy, int ox, const TapList& taps, float* stats,
                      const float* bias, int relu, const bf16* zero, hipStream_t stream, const bf16* addsrc = nullptr,
                      const BnBwdEpi* bnb = nullptr, const AffineEpi* aff = nullptr,
-                     const float* pscale = nullptr, const float* pshift = nullptr, int nbias = 0);
+                     const float* pscale = nullptr, const float* pshift = nullptr, int nbias = 0,
+                     const bf16* src2 = nullptr, int Cs2 = 0, const float* bias2 = nullptr);
+// (src2, Cs2, bias2: a second A source concatenated along K -- a 1x1 source [pixels][Cs2] on src's pixel
+// grid, Cs2 % 64 == 0, against columns T*Cs .. of the weight, then a [Co][T*Cs + Cs2] matrix; bias2, fp32
+// [Co], is added in fp32 before the output's bf16 rounding.  Plain FAST store GEMMs only; never split-K.)
 // (pscale, pshift: BN + ReLU prologue on the input of a 1x1 stride-1 forward, K5 -- the input is
 // the BN's input x and the conv sees bf16(relu(x * pscale[c] + pshift[c])))
 // backward of act(c * scale + shift [+ r]) from its output y: g = dy * act'(y) and dc = g * scale
@@ -159,6 +163,20 @@ void launch_stem_bwd_dw(const float* tot, const float* sums, const float* scale,
                         float* dw, hipStream_t s);
 int colsum_partials(int M);
 void launch_colsum(const bf16* x, int M, int C, float* part, float* out, hipStream_t s);
+// bn_lin.hip: backward of a training-mode BN behind a 1x1 stride-1 conv (width m -> C channels) as a linear
+// map of the conv's operands.  prep: coef [3][C] fp32 scratch, wcat [m][C + m] bf16 (the weight of the
+// K-concatenated dgrad GEMM over [g | a2]) and its fp32 bias [m]; dw: the weight-gradient fix-up from
+// G = g^T a2 [C][m] and A2 = a2^T a2 [m][m].  w3: [C][m] bf16 (forward layout), wt: [m][C] (transposed).
+// colsum: column sums of a2 [M][m] (part: [bn_lin_colsum_partials][m] scratch); qpart: [bn_lin_q_slices][m][m].
+bool bn_lin_supported(int m, int C);
+int bn_lin_colsum_partials(int M, int m);
+int bn_lin_q_slices(int m, int C);
+void launch_bn_lin_colsum(const bf16* a2, int M, int m, float* part, float* out, hipStream_t s);
+void launch_bn_lin_prep(const bf16* w3, const bf16* wt, const float* scale, const float* invstd, const float* sums,
+                        const float* colsum, float inv_count, int m, int C, float* coef, float* qpart, bf16* wcat,
+                        float* bias, hipStream_t s);
+void launch_bn_lin_dw(const float* G, const float* A2, const bf16* w3, const float* coef, const float* colsum,
+                      float inv_count, int m, int C, float* dw, hipStream_t s);
 void launch_bn_finalize(const float* st, int W, int C, float eps, const float* gamma, const float* beta, float* mean,
                         float* invstd, float* scale, float* shift, float* rm, float* rv, float momentum,
                         hipStream_t s, float iabn_eps = -1.f, float* rgamma = nullptr);

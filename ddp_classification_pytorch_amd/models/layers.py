@@ -37,14 +37,15 @@ class Conv2d(nn.Module):
         fan_out = self.out_channels * self.kernel_size * self.kernel_size // self.groups
         nn.init.normal_(self.weight, 0.0, math.sqrt(2.0 / fan_out))
 
-    def forward(self, x, stats=False, link=None, deposit=None):
+    def forward(self, x, stats=False, link=None, deposit=None, lin=None):
         """Returns (y, bn_stat_slabs_or_None).  `link` / `deposit`: block-input gradient
-        hand-off as primary / secondary consumer (ops.functional.GradJoin)."""
+        hand-off as primary / secondary consumer (ops.functional.GradJoin); `lin`: the
+        ops.functional.BN3Linear shared with the BN behind this conv."""
         if self.groups > 1:
             if stats:
                 return Fn.grouped_conv2d(x, self.weight, self.groups, self.stride, self.padding, stats=True)
             return Fn.grouped_conv2d(x, self.weight, self.groups, self.stride, self.padding), None
-        y, slabs = Fn.conv2d(x, self.weight, self.stride, self.padding, stats and x.is_cuda, link, deposit)
+        y, slabs = Fn.conv2d(x, self.weight, self.stride, self.padding, stats and x.is_cuda, link, deposit, lin)
         return y, (slabs if stats and x.is_cuda else None)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
@@ -90,7 +91,7 @@ class BatchNorm2d(nn.Module):
         self.iabn_eps = 1e-5
 
     def forward(self, x, slabs=None, act="relu", residual=None, slope=0.01, link=None, residual_bn=None,
-                fuse_bwd=False):
+                fuse_bwd=False, lin=None):
         """``residual_bn=(bn, rslabs)``: ``residual`` is the raw input of BatchNorm2d ``bn`` (a
         projection shortcut), normalised inside this layer's apply pass (Fn.batch_norm_add_bn_act)."""
         stats = self.training and not self.frozen
@@ -121,7 +122,7 @@ class BatchNorm2d(nn.Module):
         return Fn.batch_norm_act(x, slabs, gamma, self.bias, self.running_mean, self.running_var, stats, self.momentum,
                                  self.eps, act=act, slope=slope, residual=residual,
                                  group=self.process_group if stats else None, link=link, iabn=iabn,
-                                 fuse_bwd=fuse_bwd, rgamma=rgamma, iabn_eps=iabn_eps)
+                                 fuse_bwd=fuse_bwd, rgamma=rgamma, iabn_eps=iabn_eps, lin=lin if stats else None)
 
     def forward_pool(self, x, slabs=None, act="relu", k=3, s=2, p=1):
         """BN + act + k x k / s max pool.  Training-mode statistics with a ReLU/identity
@@ -176,7 +177,7 @@ class Linear(nn.Module):
         return f"in={self.in_features}, out={self.out_features}, bias={self.bias is not None}"
 
 
-def bn_relu_conv(bn: BatchNorm2d, conv: Conv2d, x, slabs=None, stats=False, fuse_bwd=False):
+def bn_relu_conv(bn: BatchNorm2d, conv: Conv2d, x, slabs=None, stats=False, fuse_bwd=False, lin=None):
     """conv(relu(bn(x))) where ``conv`` is the BN output's only consumer.  A training-mode BN is
     then applied inside the conv: the normalised activation is never written.
       * a 1x1 stride-1 conv (a bottleneck's bn2 -> conv3): in the GEMMs' operand registers
@@ -198,7 +199,8 @@ def bn_relu_conv(bn: BatchNorm2d, conv: Conv2d, x, slabs=None, stats=False, fuse
         bn._nbt_pending += 1
         return Fn.bn_relu_conv3x3(x, slabs, bn.weight, bn.bias, bn.running_mean, bn.running_var, True, bn.momentum,
                                   bn.eps, conv.weight, stats, group=bn.process_group)
-    return conv(bn(x, slabs, act="relu", fuse_bwd=fuse_bwd), stats=stats)
+    # (lin: only here -- the linear backward of the BN behind ``conv`` reads the materialised relu(bn(x)))
+    return conv(bn(x, slabs, act="relu", fuse_bwd=fuse_bwd), stats=stats, lin=lin)
 
 
 def conv_bn(conv: Conv2d, bn: BatchNorm2d, x, act="relu", residual=None, slope=0.01):

@@ -101,12 +101,15 @@ class Bottleneck(nn.Module):
         # bn1 + ReLU inside conv2's staged windows where the direct 64-channel 3x3 kernels run
         # (layers.bn_relu_conv); a grouped conv2 (ResNeXt) fuses bn1's backward reduction into its dgrad
         y, s = bn_relu_conv(self.bn1, self.conv2, y, s, stats=t, fuse_bwd=self.conv2.groups > 1)
+        # identity block: bn3's backward as a linear map of conv3's operands (Fn.BN3Linear) -- conv3's
+        # gradients straight from the next block's masked gradient, no input gradient of bn3
+        lin = Fn.BN3Linear() if (self.downsample is None and t and _train_stats(self.bn3)) else None
         # bn2 + ReLU run inside conv3's GEMMs (layers.bn_relu_conv): no activation pass
-        y, s = bn_relu_conv(self.bn2, self.conv3, y, s, stats=t)
+        y, s = bn_relu_conv(self.bn2, self.conv3, y, s, stats=t, lin=lin)
         if self.downsample is not None:
             r, rs = self.downsample[0](x, stats=t, deposit=join)
             return self.bn3(y, s, act="relu", residual=r, residual_bn=(self.downsample[1], rs))
-        return self.bn3(y, s, act="relu", residual=x, link=join)
+        return self.bn3(y, s, act="relu", residual=x, link=join, lin=lin)
 
 
 class ResNet(nn.Module):

@@ -332,6 +332,46 @@ def bn_source(x):
     return getattr(x, "_dcp_bnsrc", None)
 
 
+class BN3Linear:
+    """Hand-off between the last BN of an identity bottleneck (bn3, with the residual add and ReLU) and
+    the 1x1 stride-1 conv in front of it (conv3), shared by the two autograd nodes.
+
+    When bn3's backward holds the masked gradient ``g`` and its sums from the next block's dgrad
+    epilogue (:class:`BNSource`), BN backward is affine per channel and its input is conv3's own
+    output, so conv3's data and weight gradients follow from ``g``, conv3's input and small m x m
+    matrices (``conv1x1_bn_lin_bwd``, csrc/bn_lin.hip): bn3's input gradient, a block-output-wide
+    tensor written once and read twice, is never formed.  bn3's backward then leaves ``payload`` here
+    and hands ``g`` itself to conv3's backward, which takes the linear path only for exactly that
+    buffer.  Everything else -- no fused hand-off (the network's last block), SyncBN, another
+    activation -- runs the two backwards unchanged.  ``armed``: the conv accepted the hand-off (its
+    shape fits and it kept what the linear path needs); the BN offers nothing otherwise.
+    ``DCP_BN3_LINEAR=0`` switches it off (A/B)."""
+
+    __slots__ = ("payload", "armed")
+
+    def __init__(self):
+        self.payload, self.armed = None, False
+
+
+_BN3_LINEAR = [os.environ.get("DCP_BN3_LINEAR", "1") != "0"]
+
+
+def set_bn3_linear(enabled: bool):
+    _BN3_LINEAR[0] = bool(enabled)
+
+
+def bn3_linear_fits(x, conv_weight, stride, pad, groups) -> bool:
+    """Whether a conv -> BN pair takes the linear backward: a 1x1 stride-1 ungrouped conv on the GPU
+    with input and output channels in multiples of 64 (the K-concatenated GEMM's k-tiles) that expands
+    by at least 4.  The path trades three passes over the Co-wide output gradient for about four over
+    the Ci-wide input and a K longer by Ci / Co: at 4x (ResNet-50 / 101) that is -9.6 ms of a 262 ms
+    step, at 2x (ResNeXt-50 32x4d) it measured no gain (11,760 against 11,782 img/s,
+    profiles/r7/bn3_linear_ab_b4096.txt), so those keep the elementwise pass."""
+    Co, KH, KW, Ci = conv_weight.shape
+    return (_BN3_LINEAR[0] and x.is_cuda and KH == 1 and KW == 1 and stride == 1 and pad == 0 and groups == 1
+            and Ci == x.shape[-1] and Ci % 64 == 0 and Co % 64 == 0 and Co >= 4 * Ci and torch.is_grad_enabled())
+
+
 # ----------------------------------------------------------------------------- wgrad stream
 # A conv's weight gradient does not feed the rest of the backward pass, only the optimizer (and
 # the DDP buckets): with DCP_WGRAD_STREAM=1 it runs on a second HIP stream beside the data
@@ -384,11 +424,14 @@ class _WgradOnSide:
 
 class _Conv2d(Function):
     @staticmethod
-    def forward(ctx, x, weight, wb, wt, stride, pad, stats, link, bnsrc, deposit):
+    def forward(ctx, x, weight, wb, wt, stride, pad, stats, link, bnsrc, deposit, lin=None):
         y, slabs = K(x).conv_fwd(x, wb, stride, pad, stats)
-        ctx.save_for_backward(x, wt)
+        if lin is not None:
+            ctx.save_for_backward(x, wt, wb)  # (wb: the cached bf16 weight, no copy)
+        else:
+            ctx.save_for_backward(x, wt)
         ctx.geo = (weight.shape[1], weight.shape[2], stride, pad)
-        ctx.link, ctx.bnsrc, ctx.deposit = link, bnsrc, deposit
+        ctx.link, ctx.bnsrc, ctx.deposit, ctx.lin = link, bnsrc, deposit, lin
         ctx.mark_non_differentiable(slabs)
         ctx.set_materialize_grads(False)  # no zero-filled gradient for the statistics slabs
         return y, slabs
@@ -396,8 +439,24 @@ class _Conv2d(Function):
     @staticmethod
     def backward(ctx, dy, _dslabs):
         if dy is None:
-            return (None,) * 10
-        x, wt = ctx.saved_tensors
+            return (None,) * 11
+        lin, ctx.lin = ctx.lin, None
+        if lin is not None:
+            x, wt, wb = ctx.saved_tensors
+            pay, lin.payload = lin.payload, None
+            if pay is not None:
+                # the BN behind this conv handed over its masked output gradient instead of its input
+                # gradient (BN3Linear): both of this conv's gradients from it, in one op
+                g, scale, invstd, sums, count = pay
+                if g.data_ptr() != dy.data_ptr() or g.shape != dy.shape:
+                    raise RuntimeError("conv2d backward: the BN hand-off's gradient buffer was replaced")
+                dx, dw = K(dy).conv1x1_bn_lin_bwd(g, x, wb, wt, scale, invstd, sums, count,
+                                                 ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+                ctx.link = ctx.bnsrc = ctx.deposit = None
+                return (dx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
+                        None, None, None, None, None, None, None, None, None)
+        else:
+            x, wt = ctx.saved_tensors
         KH, KW, stride, pad = ctx.geo
         dy = dy.contiguous()
         k = K(dy)
@@ -445,11 +504,11 @@ class _Conv2d(Function):
             dw = k.conv_wgrad(dy, x, KH, KW, stride, pad)
         side.join()
         ctx.link = ctx.bnsrc = ctx.deposit = None
-        return dx, dw, None, None, None, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None, None, None, None
 
 
 def conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1, pad: int = 0, stats: bool = False,
-           link: "GradJoin | None" = None, deposit: "GradJoin | None" = None):
+           link: "GradJoin | None" = None, deposit: "GradJoin | None" = None, lin: "BN3Linear | None" = None):
     """NHWC conv; returns (y, bn_stat_slabs).  weight: fp32 [Co,KH,KW,Ci].
 
     `link`: the block's GradJoin when this conv is the primary consumer of the block input
@@ -462,7 +521,11 @@ def conv2d(x: torch.Tensor, weight: torch.Tensor, stride: int = 1, pad: int = 0,
         weight = F.pad(weight, (0, x.shape[3] - weight.shape[3]))  # autograd view for the padded dW
         return _Conv2d.apply(x, weight, wb, wt, stride, pad, stats, link, None, deposit)
     wb, wt = prepared_weight(weight, 0, True)
-    return _Conv2d.apply(x, weight, wb, wt, stride, pad, stats, link, bnsrc, deposit)
+    if lin is not None and not (link is None and deposit is None and bn3_linear_fits(x, weight, stride, pad, 1)):
+        lin = None
+    if lin is not None:
+        lin.armed = True
+    return _Conv2d.apply(x, weight, wb, wt, stride, pad, stats, link, bnsrc, deposit, lin)
 
 
 class _GroupedConv2d(Function):
@@ -653,7 +716,7 @@ def _check_equal_counts(gathered, count):
 
 class _BNAct(Function):
     @staticmethod
-    def forward(ctx, x, slabs, gamma, beta, res, run_mean, run_var, cfg: BNConfig, link, src):
+    def forward(ctx, x, slabs, gamma, beta, res, run_mean, run_var, cfg: BNConfig, link, src, lin=None):
         k = K(x)
         C = x.shape[-1]
         count = x.numel() // C
@@ -693,6 +756,7 @@ class _BNAct(Function):
         ctx.has_res = res is not None
         ctx.link = link
         ctx.src = src
+        ctx.lin = lin
         if src is not None:
             src.tensors = (x, res, scale, shift, mean, invstd, mask)
         return y
@@ -707,6 +771,7 @@ class _BNAct(Function):
         fused = src.fused if src is not None else None
         if src is not None:
             src.release()
+        lin, ctx.lin = ctx.lin, None
         want_dres = ctx.has_res and ctx.needs_input_grad[4]
         if cfg.iabn:
             y, beta = x, mean  # saved (y, beta) in place of (x, mean)
@@ -734,7 +799,7 @@ class _BNAct(Function):
                 else:
                     dgamma = local[1]
             dbeta = local[0] if (local is not None and ctx.needs_input_grad[3]) else None
-            return dx, None, dgamma, dbeta, None, None, None, None, None, None
+            return dx, None, dgamma, dbeta, None, None, None, None, None, None, None
         if fused is not None and fused[0].data_ptr() == dy.data_ptr() and fused[0].shape == dy.shape:
             # the consuming conv's dgrad epilogue already masked the gradient and reduced it
             g, local = fused
@@ -744,8 +809,15 @@ class _BNAct(Function):
                 _peer.all_reduce(sums, cfg.group)
             # ReLU / identity: g is already masked; leaky: g is raw and the elementwise pass applies act'
             post_act = cfg.act if cfg.act == 2 else 0
-            dx, _ = k.bn_bwd_elemt(g, x, None, scale, shift, mean, invstd, sums, float(ctx.count), post_act,
-                                   cfg.slope, False)
+            if (lin is not None and cfg.group is None and cfg.training_stats and post_act == 0
+                    and ctx.needs_input_grad[0] and _BN3_LINEAR[0]):
+                # the 1x1 conv that produced x takes g and the sums themselves (BN3Linear): no
+                # elementwise pass, no input gradient of this BN
+                lin.payload = (g, scale, invstd, sums, float(ctx.count))
+                dx = g
+            else:
+                dx, _ = k.bn_bwd_elemt(g, x, None, scale, shift, mean, invstd, sums, float(ctx.count), post_act,
+                                       cfg.slope, False)
             dres = g if want_dres else None
         else:
             need_affine = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
@@ -766,7 +838,7 @@ class _BNAct(Function):
         if dres is not None and ctx.link is not None:
             dres = ctx.link.deposit(dres)  # summed into the block input gradient by the first conv's dgrad
         ctx.link = None
-        return dx, None, dgamma, dbeta, dres, None, None, None, None, None
+        return dx, None, dgamma, dbeta, dres, None, None, None, None, None, None
 
 
 # ----------------------------------------------------------------------------- BN + ReLU as a conv prologue
@@ -1077,7 +1149,7 @@ def iabn_fold_enabled() -> bool:
 
 def batch_norm_act(x, slabs, gamma, beta, run_mean, run_var, training_stats, momentum, eps, act="relu",
                    slope=0.01, residual=None, group=None, link=None, iabn=False, fuse_bwd=False, rgamma=None,
-                   iabn_eps=None):
+                   iabn_eps=None, lin=None):
     """``iabn``: InplaceABN storage (invertible act: identity / leaky, no residual, a gamma bounded
     away from 0 -- BatchNorm2d passes |gamma| + eps, the inplace_abn convention; with ``iabn_eps``
     (training statistics only) it passes the RAW weight and the kernels apply |gamma| + iabn_eps and
@@ -1102,7 +1174,9 @@ def batch_norm_act(x, slabs, gamma, beta, run_mean, run_var, training_stats, mom
                             (cfg.act == 2 and residual is None and _FUSE_LEAKY[0]))
     if training_stats and fusable and _FUSE_BN_BWD[0] and torch.is_grad_enabled():
         src = BNSource(cfg.act, cfg.slope)
-    out = _BNAct.apply(x, slabs, gamma, beta, residual, run_mean, run_var, cfg, link, src)
+    if lin is not None and (not lin.armed or src is None or iabn or group is not None or not x.is_cuda):
+        lin = None  # (no fused hand-off can reach this BN's backward)
+    out = _BNAct.apply(x, slabs, gamma, beta, residual, run_mean, run_var, cfg, link, src, lin)
     if src is not None:
         out._dcp_bnsrc = src
     return out
