@@ -1976,6 +1976,10 @@ void mt_adam(const Tensor& table, const Tensor& chunks, double lr, double beta1,
   h.grad_scale = grad_scale;
   h.bc1 = 1.0 - std::pow(beta1, (double)step);
   h.bc2 = 1.0 - std::pow(beta2, (double)step);
+  h.omb1 = 1.0 - beta1;
+  h.omb2 = 1.0 - beta2;
+  h.lb1 = std::log(beta1);
+  h.lb2 = std::log(beta2);
   h.decoupled = decoupled ? 1 : 0;
   dcp::launch_mt_adam(reinterpret_cast<const dcp::MTEntry*>(table.data_ptr()),
                       reinterpret_cast<const int2*>(chunks.data_ptr()), chunks.size(0), h, cur_stream());

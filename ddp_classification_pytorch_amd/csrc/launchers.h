@@ -256,6 +256,9 @@ struct SgdHyper {
 };
 struct AdamHyper {
   float lr, beta1, beta2, eps, wd, grad_scale, bc1, bc2;
+  // 1 - beta and log(beta), formed in double from the caller's beta and then rounded: 1.f - (float)0.999
+  // is 1.3e-5 off 1 - 0.999 (the second moment and, with logf of the rounded beta, the bias correction)
+  float omb1, omb2, lb1, lb2;
   int decoupled;
   const int* step_dev;  // optional device step count: bc1/bc2 computed in-kernel from it
 };

@@ -1618,7 +1618,12 @@ def arcface_rows(x, weight, labels, s=30.0, m=0.5, easy_margin=True, with_margin
     if with_margin:
         loss, rank, _, _ = k.arcface_fwd(cos, labels, C, s, m, easy_margin, False)
         return loss, rank
-    return k.xent_fwd(cos[:, :C] * s if not x.is_cuda else cos[:, :C], labels, C, 0.0)
+    if x.is_cuda:
+        # the margin kernel with m = 0 (phi = cos exactly): it applies the scale s.  (xent_fwd on the
+        # raw bf16 cosines ranked them right but reported the loss of the UNscaled logits.)
+        loss, rank, _, _ = k.arcface_fwd(cos, labels, C, s, 0.0, True, False)
+        return loss, rank
+    return k.xent_fwd(cos[:, :C] * s, labels, C, 0.0)
 
 
 class _LogSoftmax(Function):

@@ -53,6 +53,8 @@ def test_tresnet_memorises_batch():
 def test_tresnet_inplace_abn_saves_activation_memory():
     """InplaceABN storage keeps one activation less per leaky BN layer: the peak memory of a
     TResNet-M training step drops against the same net storing the BN inputs."""
+    import gc
+
     import torch
 
     from ddp_classification_pytorch_amd.models import build_model
@@ -69,6 +71,10 @@ def test_tresnet_inplace_abn_saves_activation_memory():
         imgs = torch.randint(0, 256, (64, 3, 224, 224), dtype=torch.uint8, device=dev)
         labels = torch.randint(0, 100, (64,), device=dev)
         x = Fn.to_device_nhwc(imgs, (0.5, 0.5, 0.5), (0.25, 0.25, 0.25), cpad=3, nchw=True, in_scale=1 / 255.0)
+        # earlier tests' workload runs leave their models and graphs in reference cycles (over 1 GB by
+        # now): collected here, not by a collector pass inside the measured step, which would free
+        # them below ``base`` and shrink that step's apparent peak
+        gc.collect()
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats(dev)
         base = torch.cuda.memory_allocated(dev)
