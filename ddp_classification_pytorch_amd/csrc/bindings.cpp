@@ -544,20 +544,27 @@ Tensor conv_dgrad(const Tensor& dy, const Tensor& wt, int64_t H, int64_t W, int6
 // Stride-1 dgrad fused with the backward reduction of the BN(+ReLU)(+residual) layer that
 // produced this conv's input (y = that layer's BN input).  Returns the activation-masked
 // input gradient g' [N,H,W,C] and the per-channel sums [2,C] = (sum g', sum g'*xhat).
+// Without y (legal only with ReLU mask bits) the BN input is not read: sums[1] comes back as zeros, for a
+// caller that forms sum g'*xhat elsewhere (bn_lin_s2); g' and sums[0] are bit-identical to the call with y.
 std::tuple<Tensor, Tensor> conv_dgrad_bn(const Tensor& dy, const Tensor& wt, int64_t pad, const optional<Tensor>& add,
-                                         const Tensor& y, const optional<Tensor>& res, const Tensor& scale,
+                                         const optional<Tensor>& y, const optional<Tensor>& res, const Tensor& scale,
                                          const Tensor& shift, const Tensor& mean, const Tensor& invstd, int64_t act,
                                          const optional<Tensor>& mask, double slope) {
   CHECK_ACT(dy);
   CHECK_ACT(wt);
-  CHECK_ACT(y);
   const int N = dy.size(0), Ho = dy.size(1), Wo = dy.size(2), Co = dy.size(3);
   const int C = wt.size(0), KH = wt.size(1), KW = wt.size(2);
   TORCH_CHECK(wt.size(3) == Co, "transposed weight Co mismatch");
   TORCH_CHECK(C % 8 == 0 && Co % 8 == 0, "conv_dgrad_bn needs channel multiples of 8");
-  TORCH_CHECK(y.dim() == 4 && y.size(0) == N && y.size(3) == C, "conv_dgrad_bn: BN input shape");
-  const int H = y.size(1), W = y.size(2);
-  TORCH_CHECK(H + 2 * pad - KH + 1 == Ho && W + 2 * pad - KW + 1 == Wo, "conv_dgrad_bn: stride-1 geometry");
+  const int H = Ho - 2 * (int)pad + KH - 1, W = Wo - 2 * (int)pad + KW - 1;  // stride 1
+  TORCH_CHECK(H > 0 && W > 0, "conv_dgrad_bn: stride-1 geometry");
+  if (y.has_value()) {
+    CHECK_ACT(*y);
+    TORCH_CHECK(y->dim() == 4 && y->size(0) == N && y->size(3) == C, "conv_dgrad_bn: BN input shape");
+    TORCH_CHECK(y->size(1) == H && y->size(2) == W, "conv_dgrad_bn: stride-1 geometry");
+  } else {
+    TORCH_CHECK(mask.has_value() && act == 1, "conv_dgrad_bn: no BN input needs ReLU mask bits");
+  }
   TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv_dgrad_bn: too many pixels");
   TORCH_CHECK(act == 0 || act == 1 || act == 2, "conv_dgrad_bn: act must be none, ReLU or leaky ReLU");
   TORCH_CHECK(act != 2 || (!mask.has_value() && !res.has_value()), "conv_dgrad_bn: leaky path has no mask / residual");
@@ -612,7 +619,7 @@ std::tuple<Tensor, Tensor> conv_dgrad_bn(const Tensor& dy, const Tensor& wt, int
       t.dx[i] = pad - kw;
       t.widx[i] = i;
     }
-  dcp::BnBwdEpi e{bp(y), resp, scale.data_ptr<float>(), shift.data_ptr<float>(), mean.data_ptr<float>(),
+  dcp::BnBwdEpi e{y.has_value() ? bp(*y) : nullptr, resp, scale.data_ptr<float>(), shift.data_ptr<float>(), mean.data_ptr<float>(),
                   invstd.data_ptr<float>(), part.data_ptr<float>(), (int)act, maskp, (float)slope, add_s2, add_hc,
                   add_wc};
   auto st = cur_stream();
@@ -778,9 +785,11 @@ Tensor conv1x1_cat(const Tensor& x, const optional<Tensor>& x2, const Tensor& w,
 // from the masked gradient g of the BN's output and its sums [2,C] = (sum g, sum g xhat) (bn_lin.hip):
 // the BN's input gradient is never formed.  w3: [C,1,1,m] bf16, wt: [m,1,1,C] bf16 (its transpose).
 // Returns (d_a2 [N,H,W,m] bf16, dW3 [C,1,1,m] fp32); either may be skipped (an empty tensor).
+// G = g^T a2 [C,1,1,m] and colsum(a2) [m], when the caller already holds them (bn_lin_s2), are not recomputed.
 std::tuple<Tensor, Tensor> conv1x1_bn_lin_bwd(const Tensor& g, const Tensor& a2, const Tensor& w3, const Tensor& wt,
                                               const Tensor& scale, const Tensor& invstd, const Tensor& sums,
-                                              double count, bool need_dx, bool need_dw) {
+                                              double count, bool need_dx, bool need_dw, const optional<Tensor>& Gin,
+                                              const optional<Tensor>& colsum_in) {
   CHECK_ACT(g);
   CHECK_ACT(a2);
   CHECK_ACT(w3);
@@ -805,8 +814,19 @@ std::tuple<Tensor, Tensor> conv1x1_bn_lin_bwd(const Tensor& g, const Tensor& a2,
   auto st = cur_stream();
   const int M = N * H * W;
   TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv1x1_bn_lin_bwd: too many pixels");
-  auto cs = at::empty({m}, f32_like(g));
-  {
+  for (const optional<Tensor>* t : {&Gin, &colsum_in}) {
+    if (!t->has_value()) continue;
+    CHECK_DEV(**t);
+    CHECK_CONTIG(**t);
+    CHECK_F32(**t);
+  }
+  TORCH_CHECK(!Gin.has_value() || Gin->numel() == (int64_t)C * m, "conv1x1_bn_lin_bwd: G is [C,1,1,m]");
+  TORCH_CHECK(!colsum_in.has_value() || colsum_in->numel() == m, "conv1x1_bn_lin_bwd: colsum is [m]");
+  Tensor cs;
+  if (colsum_in.has_value()) {
+    cs = *colsum_in;
+  } else {
+    cs = at::empty({m}, f32_like(g));
     auto part = at::empty({dcp::bn_lin_colsum_partials(M, m), m}, f32_like(g));
     dcp::launch_bn_lin_colsum(bp(a2), M, m, part.data_ptr<float>(), cs.data_ptr<float>(), st);
   }
@@ -820,13 +840,48 @@ std::tuple<Tensor, Tensor> conv1x1_bn_lin_bwd(const Tensor& g, const Tensor& a2,
   Tensor dx = at::empty({0}, bf16_like(g)), dw = at::empty({0}, f32_like(g));
   if (need_dx) dx = conv1x1_cat(g, a2, wcat, bias);
   if (need_dw) {
-    const Tensor G = conv_wgrad(g, a2, 1, 1, 1, 0);    // [C,1,1,m]
+    const Tensor G = Gin.has_value() ? *Gin : conv_wgrad(g, a2, 1, 1, 1, 0);  // [C,1,1,m]
     const Tensor A2 = conv_wgrad(a2, a2, 1, 1, 1, 0);  // [m,1,1,m]
     dw = at::empty({C, 1, 1, m}, f32_like(g));
     dcp::launch_bn_lin_dw(G.data_ptr<float>(), A2.data_ptr<float>(), bp(w3), coef.data_ptr<float>(),
                           cs.data_ptr<float>(), inv_count, m, C, dw.data_ptr<float>(), st);
   }
   return {dx, dw};
+}
+
+// sum g xhat of a training-mode BN behind a 1x1 stride-1 conv (a2 [N,H,W,m] -> C channels), without the BN's
+// input: from G = g^T a2 (the conv's weight-gradient GEMM, computed here) and colsum(a2) (bn_lin.hip).
+// sums [2,C]: row 0 = sum g is read, row 1 is WRITTEN in place, on the current stream.  Returns (G [C,1,1,m]
+// fp32, colsum [m] fp32) for conv1x1_bn_lin_bwd, which then recomputes neither.
+std::tuple<Tensor, Tensor> bn_lin_s2(const Tensor& g, const Tensor& a2, const Tensor& w3, const Tensor& invstd,
+                                     const Tensor& sums, double count) {
+  CHECK_ACT(g);
+  CHECK_ACT(a2);
+  CHECK_ACT(w3);
+  TORCH_CHECK(g.dim() == 4 && a2.dim() == 4, "bn_lin_s2 expects NHWC tensors");
+  const int N = g.size(0), H = g.size(1), W = g.size(2), C = g.size(3), m = a2.size(3);
+  TORCH_CHECK(a2.size(0) == N && a2.size(1) == H && a2.size(2) == W, "bn_lin_s2: a2 grid");
+  TORCH_CHECK(dcp::bn_lin_supported(m, C), "bn_lin_s2: channels must be multiples of 64");
+  TORCH_CHECK(w3.numel() == (int64_t)C * m && w3.size(0) == C, "bn_lin_s2: weight shape");
+  CHECK_DEV(invstd);
+  CHECK_CONTIG(invstd);
+  CHECK_F32(invstd);
+  CHECK_DEV(sums);
+  CHECK_CONTIG(sums);
+  CHECK_F32(sums);
+  TORCH_CHECK(invstd.numel() == C && sums.numel() == 2 * (int64_t)C && count > 0, "bn_lin_s2: invstd [C], sums [2,C]");
+  TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "bn_lin_s2: too many pixels");
+  const int M = N * H * W;
+  auto st = cur_stream();
+  auto cs = at::empty({m}, f32_like(g));
+  {
+    auto part = at::empty({dcp::bn_lin_colsum_partials(M, m), m}, f32_like(g));
+    dcp::launch_bn_lin_colsum(bp(a2), M, m, part.data_ptr<float>(), cs.data_ptr<float>(), st);
+  }
+  const Tensor G = conv_wgrad(g, a2, 1, 1, 1, 0);
+  dcp::launch_bn_lin_s2(G.data_ptr<float>(), bp(w3), cs.data_ptr<float>(), invstd.data_ptr<float>(),
+                        (float)(1.0 / count), m, C, sums.data_ptr<float>(), st);
+  return {G, cs};
 }
 
 // weight gradient for conv_fwd_geo's geometry (output grid taken from dy)
@@ -2089,7 +2144,7 @@ TORCH_LIBRARY(dcp, m) {
   m.def("conv_fwd(Tensor x, Tensor w, int stride, int pad, bool stats) -> (Tensor, Tensor)", &conv_fwd);
   m.def("conv_dgrad(Tensor dy, Tensor wt, int H, int W, int stride, int pad, Tensor? add=None) -> Tensor", &conv_dgrad);
   m.def(
-      "conv_dgrad_bn(Tensor dy, Tensor wt, int pad, Tensor? add, Tensor y, Tensor? res, Tensor scale, Tensor shift, "
+      "conv_dgrad_bn(Tensor dy, Tensor wt, int pad, Tensor? add, Tensor? y, Tensor? res, Tensor scale, Tensor shift, "
       "Tensor mean, Tensor invstd, int act, Tensor? mask=None, float slope=0.0) -> (Tensor, Tensor)",
       &conv_dgrad_bn);
   m.def("conv_wgrad(Tensor dy, Tensor x, int KH, int KW, int stride, int pad) -> Tensor", &conv_wgrad);
@@ -2111,8 +2166,10 @@ TORCH_LIBRARY(dcp, m) {
   m.def("conv1x1_cat(Tensor x, Tensor? x2, Tensor w, Tensor? bias) -> Tensor", &conv1x1_cat);
   m.def(
       "conv1x1_bn_lin_bwd(Tensor g, Tensor a2, Tensor w3, Tensor wt, Tensor scale, Tensor invstd, Tensor sums, "
-      "float count, bool need_dx, bool need_dw) -> (Tensor, Tensor)",
+      "float count, bool need_dx, bool need_dw, Tensor? G=None, Tensor? colsum=None) -> (Tensor, Tensor)",
       &conv1x1_bn_lin_bwd);
+  m.def("bn_lin_s2(Tensor g, Tensor a2, Tensor w3, Tensor invstd, Tensor(a!) sums, float count) -> (Tensor, Tensor)",
+        &bn_lin_s2);
   m.def(
       "bn_stats_finalize(Tensor x, Tensor? slabs, Tensor? gamma, Tensor? beta, Tensor? run_mean, Tensor? run_var, "
       "float momentum, float eps, float iabn_eps=-1., Tensor(a!)? rgamma_out=None) -> (Tensor, Tensor, Tensor, Tensor)",

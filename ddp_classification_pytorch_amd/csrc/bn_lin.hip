@@ -143,6 +143,29 @@ __global__ void __launch_bounds__(256) bn_lin_colsum_kernel(const bf16* __restri
     }
 }
 
+// sums[1][c] = S2[c] = sum g xhat = invstd[c] * sum_k W3[c][k] * (G[c][k] - S1[c] * colmean[k]),  S1 = sums[0]:
+// the BN input is x3 = a2 W3^T, so sum_rows g (x3 - mean) = W3 (g^T a2 - S1 (x) colmean(a2)) row by row -- from
+// the weight-gradient GEMM's G = g^T a2 [C][m] instead of a pass over x3 (the dgrad epilogue that hands g
+// over then loads no BN-input rows, conv_igemm.hip EPI 5).  The difference is taken per k, before the
+// sum: each term is a centred covariance, so a BN input whose mean is large against its spread cancels
+// nothing here.  One wave per channel, lanes strided over k, fixed-order shuffle reduction (deterministic).
+__global__ void __launch_bounds__(256) bn_lin_s2_kernel(const float* __restrict__ G, const bf16* __restrict__ w3,
+                                                        const float* __restrict__ colsum,
+                                                        const float* __restrict__ invstd, float inv_count, int m,
+                                                        int C, float* __restrict__ sums) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= C) return;
+  const float s1 = sums[c];
+  const float* g = G + (size_t)c * m;
+  const bf16* w = w3 + (size_t)c * m;
+  float s = 0.f;
+  for (int k = lane; k < m; k += 64) s = fmaf(bf2f(w[k]), fmaf(-s1, colsum[k] * inv_count, g[k]), s);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) sums[C + c] = s * invstd[c];
+}
+
 // bias[j] = -( sum_k colmean[k] * Qr[j][k] + sum_c e[c] * wt[j][c] ),  Qr = the ROUNDED Q of wcat's row j
 // (exactly what the GEMM multiplies a2 with).  One wave per j, fixed-order shuffle reduction.
 __global__ void __launch_bounds__(256) bn_lin_bias_kernel(const bf16* __restrict__ wt, const bf16* __restrict__ wcat,
@@ -237,6 +260,13 @@ void launch_bn_lin_colsum(const bf16* a2, int M, int m, float* part, float* out,
   const int P = bn_lin_colsum_partials(M, m);
   hipLaunchKernelGGL(bn_lin_colsum_kernel, dim3(P), dim3(256), 0, s, a2, M, m, part);
   launch_partial_sum(part, P, m, out, s);
+}
+
+// sums: [2][C] fp32, row 0 = S1 read, row 1 = S2 written; G: [C][m] fp32 = g^T a2; colsum: [m]
+void launch_bn_lin_s2(const float* G, const bf16* w3, const float* colsum, const float* invstd, float inv_count,
+                      int m, int C, float* sums, hipStream_t s) {
+  hipLaunchKernelGGL(bn_lin_s2_kernel, dim3((C + 3) / 4), dim3(256), 0, s, G, w3, colsum, invstd, inv_count, m, C,
+                     sums);
 }
 
 // coef: [3][C] fp32 scratch (kept for launch_bn_lin_dw); qpart: [bn_lin_q_slices(m, C)][m][m] fp32 scratch;

@@ -637,11 +637,16 @@ tap_gemm_kernel(const TapGemmParams p) {
       }
   }
 
-  if constexpr (EPI == 3 || EPI == 4) {
+  if constexpr (EPI == 3 || EPI == 4 || EPI == 5) {
     // ---- dgrad + fused BN backward (stride 1: dst rows == GEMM rows) ----
     // EPI 4: the activation mask comes as bits (bn_act_mask) instead of being recomputed from
     // the BN input and the residual -- no residual rows, no scale/shift registers.
-    constexpr bool MASKED = EPI == 4;
+    // EPI 5: EPI 4 without the sum of g * xhat -- the BN input, a block-output-wide tensor whose only
+    // use here is that sum, is not loaded (its owner forms the sum from the weight-gradient GEMM of
+    // the conv in front of the BN, bn_lin.hip).  The stored g and the S1 partials are EPI 4's bit for
+    // bit (same row batches, same reduction order); the S2 partials are written as zeros.
+    constexpr bool MASKED = EPI >= 4;
+    constexpr bool XHAT = EPI != 5;
     constexpr int RB = BN * 2, NCH = BN / 8, R = 256 / NCH, RPT = BM / R;
     char* E = smem;
     const int c = tid % NCH, pr0 = tid / NCH;
@@ -674,7 +679,7 @@ tap_gemm_kernel(const TapGemmParams p) {
         sc[e] = cok ? p.bnb.scale[cg + e] : 0.f;
         sh[e] = cok ? p.bnb.shift[cg + e] : 0.f;
       }
-      mu[e] = cok ? p.bnb.mean[cg + e] : 0.f;
+      if constexpr (XHAT) mu[e] = cok ? p.bnb.mean[cg + e] : 0.f;
     }
 #pragma unroll
     for (int b = 0; b < RPT / RBATCH; ++b) {
@@ -685,7 +690,7 @@ tap_gemm_kernel(const TapGemmParams p) {
         const int m = m0 + pr0 + (b * RBATCH + q) * R;
         const bool ok = m < p.M && cok;
         const size_t off = (size_t)(ok ? m : 0) * p.Co + (cok ? cg : 0);
-        yv[q] = ok ? *(const bf16x8*)(p.bnb.y + off) : bf16x8{};
+        if constexpr (XHAT) yv[q] = ok ? *(const bf16x8*)(p.bnb.y + off) : bf16x8{};
         if (has_res) rv[q] = ok ? *(const bf16x8*)(p.bnb.res + off) : bf16x8{};
         if (has_add) {
           if (p.bnb.add_s2 == 0) {
@@ -716,7 +721,8 @@ tap_gemm_kernel(const TapGemmParams p) {
           for (int e = 0; e < 8; ++e) {
             float g = bf2f(v[e]);
             if (has_add) g = bf2f(f2bf(g + bf2f(av[q][e])));  // the rounding of the unfused add
-            const float yf = bf2f(yv[q][e]);
+            float yf = 0.f;
+            if constexpr (XHAT) yf = bf2f(yv[q][e]);
             float gd = 1.f;  // act'(z) for the leaky sums (the stored gradient stays raw)
             if (MASKED) {
               if (p.bnb.act == 1 && !((mk[q] >> e) & 1u)) g = 0.f;
@@ -729,7 +735,7 @@ tap_gemm_kernel(const TapGemmParams p) {
             o[e] = f2bf(g);
             const float gr = bf2f(o[e]) * gd;
             s1[e] += gr;
-            s2[e] += gr * (yf - mu[e]);
+            if constexpr (XHAT) s2[e] += gr * (yf - mu[e]);
           }
           *(bf16x8*)(p.dst + (size_t)m * p.Co + cg) = o;
         }
@@ -745,7 +751,7 @@ tap_gemm_kernel(const TapGemmParams p) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       red[(0 * 8 + e) * SE + pr0 * NCH + c] = s1[e];
-      red[(1 * 8 + e) * SE + pr0 * NCH + c] = s2[e];
+      if constexpr (XHAT) red[(1 * 8 + e) * SE + pr0 * NCH + c] = s2[e];
     }
     __syncthreads();
     if (tid < 2 * BN) {
@@ -753,9 +759,11 @@ tap_gemm_kernel(const TapGemmParams p) {
       if (n0 + ch < p.Co) {
         const float* col = red + (which * 8 + (ch & 7)) * SE + (ch >> 3);
         float t = 0.f;
+        if (XHAT || !which) {
 #pragma unroll 4
-        for (int r = 0; r < R; ++r) t += col[r * NCH];
-        if (which) t *= p.bnb.invstd[n0 + ch];
+          for (int r = 0; r < R; ++r) t += col[r * NCH];
+        }
+        if (XHAT && which) t *= p.bnb.invstd[n0 + ch];
         p.bnb.part[((size_t)tm * 2 + which) * p.Co + n0 + ch] = t;
       }
     }
@@ -2039,7 +2047,7 @@ static void launch_tg(TapGemmParams p, int grid, hipStream_t stream) {
   if (EPI == 0) epi = (size_t)128 * 2 * BN;
   if (EPI == 1) epi = (size_t)128 * 2 * BN;  // tile_stats128_vv keeps its scratch inside the image
   // image, then the sums' [2][8][256 + 4] fp32 in its space
-  if (EPI == 3 || EPI == 4) epi = std::max((size_t)128 * 2 * BN, (size_t)2 * 8 * 260 * 4);
+  if (EPI == 3 || EPI == 4 || EPI == 5) epi = std::max((size_t)128 * 2 * BN, (size_t)2 * 8 * 260 * 4);
   size_t lds = std::max((size_t)std::min(NS, std::max(p.nkt, 1)) * stage, epi);
   if (!FAST) lds = std::max(lds, full + kMaxTaps * sizeof(int));  // LDS tap table behind the stages
   // BN-prologue (scale, shift) table behind the stages in use
@@ -2248,6 +2256,13 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
       abort();
     }
     epi = bnb->mask != nullptr ? 4 : 3;
+    if (bnb->y == nullptr) {  // no BN input: the masked epilogue without the xhat sum (ReLU bits only)
+      if (bnb->mask == nullptr || bnb->act != 1) {
+        fprintf(stderr, "launch_tap_gemm: a fused BN backward without the BN input needs ReLU mask bits\n");
+        abort();
+      }
+      epi = 5;
+    }
   }
   const bool fast = (p.cpt & 7) == 0 && taps.n <= 32;  // FAST: 32-bit tap-validity masks
   if (src2 != nullptr && !(fast && epi == 0 && aff == nullptr && pscale == nullptr && Cs2 > 0 && Cs2 % 64 == 0 &&
@@ -2376,6 +2391,7 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   else if (epi == 1) { DCP_TG_NS(BN_, 1, FAST_) }  \
   else if (epi == 3) { DCP_TG_NS(BN_, 3, FAST_) }  \
   else if (epi == 4) { DCP_TG_NS(BN_, 4, FAST_) }  \
+  else if (epi == 5) { DCP_TG_NS(BN_, 5, FAST_) }  \
   else { DCP_TG_NS(BN_, 2, FAST_) }
   if (bn == 64) {
     if (fast) { DCP_TG_EPI(64, true) } else { DCP_TG_EPI(64, false) }
@@ -2496,10 +2512,12 @@ void launch_tap_gemm(const bf16* src, int N, int Hs, int Ws, int Cs,
     run();
     return;
   }
+  // (the BN-backward digit: 1 recomputed mask, 2 mask bits, 3 mask bits without the BN input -- a value of
+  // its own, so the keys of every other problem, and caches recorded with them, stay as they were)
   char kb[512];
   int len = snprintf(kb, sizeof(kb), "%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d|%d%d%d%d%d%d|", N, Hs, Ws, Cs, Co,
                      T, Hd, Wd, Hy, Wy, ss, ds, oy, ox, taps.n, stats != nullptr, bias != nullptr, relu,
-                     addsrc != nullptr, bnb ? (bnb->mask ? 2 : 1) : 0, aff != nullptr);
+                     addsrc != nullptr, bnb ? (bnb->y == nullptr ? 3 : (bnb->mask ? 2 : 1)) : 0, aff != nullptr);
   for (int i = 0; i < taps.n && len < (int)sizeof(kb) - 16; ++i)
     len += snprintf(kb + len, sizeof(kb) - len, "%d,%d,%d;", taps.dy[i], taps.dx[i], taps.widx[i]);
   // a second source is a field of its own (single-source keys keep their form: earlier caches stay valid

@@ -28,7 +28,7 @@ struct TapList {
 //   part[tile][0][c] = sum g',  part[tile][1][c] = sum g' * (y - mean) * invstd  (per 128-row tile)
 // so the separate BN backward reduction pass (re-reading g and y) disappears.
 struct BnBwdEpi {
-  const bf16* y;        // BN input [M][C]
+  const bf16* y;        // BN input [M][C]; nullptr (with mask, act 1): not read, the xhat partials are zeros
   const bf16* res;      // residual added before the activation, or nullptr
   const float* scale;   // gamma * invstd
   const float* shift;   // beta - mean * scale
@@ -177,6 +177,9 @@ void launch_bn_lin_prep(const bf16* w3, const bf16* wt, const float* scale, cons
                         float* bias, hipStream_t s);
 void launch_bn_lin_dw(const float* G, const float* A2, const bf16* w3, const float* coef, const float* colsum,
                       float inv_count, int m, int C, float* dw, hipStream_t s);
+// s2: sums[1][c] = invstd[c] sum_k w3[c][k] (G[c][k] - sums[0][c] colsum[k] / n) (sum g xhat without the BN input)
+void launch_bn_lin_s2(const float* G, const bf16* w3, const float* colsum, const float* invstd, float inv_count,
+                      int m, int C, float* sums, hipStream_t s);
 void launch_bn_finalize(const float* st, int W, int C, float eps, const float* gamma, const float* beta, float* mean,
                         float* invstd, float* scale, float* shift, float* rm, float* rv, float momentum,
                         hipStream_t s, float iabn_eps = -1.f, float* rgamma = nullptr);

@@ -71,7 +71,18 @@ def conv_dgrad_bn(dy, wt, pad, add, y, res, scale, shift, mean, invstd, act, mas
     -> (gradient, [2, C] = (sum g', sum g' * xhat)) with g' = act'(z) * dgrad.  ReLU / identity
     return g' itself (masking is idempotent); leaky ReLU returns the RAW dgrad (its BN backward
     re-applies act', so any other consumer's gradient can still be added).  ``mask``: the
-    activation mask bits from :func:`bn_act_mask` (then ``res`` is not read)."""
+    activation mask bits from :func:`bn_act_mask` (then ``res`` is not read).  ``y`` None (ReLU mask
+    bits only): the BN input is not read and row 1 of the sums is zeros."""
+    if y is None:
+        assert mask is not None and act == ACT_RELU, "no BN input needs ReLU mask bits"
+        H, W = (dy.shape[i] - 2 * pad + wt.shape[i] - 1 for i in (1, 2))
+        if add is not None and add.shape[1:3] != (H, W):
+            full = add.new_zeros((add.shape[0], H, W, add.shape[3]))
+            full[:, ::2, ::2] = add
+            add = full
+        out = (_f(conv_dgrad(dy, wt, H, W, 1, pad, add)) * unpack_mask(mask)).to(dy.dtype)
+        s1 = _rows(_f(out)).sum(0)
+        return out, torch.stack([s1, torch.zeros_like(s1)])
     if add is not None and add.shape != y.shape:  # compact stride-2 add source (StridedGrad)
         full = add.new_zeros(y.shape)
         full[:, ::2, ::2] = add

@@ -266,14 +266,20 @@ class BNSource:
     one elementwise pass -- no separate reduction pass re-reading the gradient and the BN
     input.  ``fused`` keeps a reference to the masked gradient, which also stops autograd
     from accumulating another consumer's gradient into that buffer in place; the BN
-    backward uses the fused result only if it receives exactly that buffer."""
+    backward uses the fused result only if it receives exactly that buffer.
 
-    __slots__ = ("tensors", "act", "slope", "fused")
+    ``no_xhat`` (set at forward time, :class:`BN3Linear`): the BN can form sum g' xhat without its
+    input, so the consuming conv passes no BN input to its epilogue -- that read, a pass over a
+    block-output-wide tensor, was the epilogue's only use of it -- and sets ``s2_absent``: row 1 of
+    the fused sums is then zeros until the BN's backward fills it (or replaces the sums)."""
+
+    __slots__ = ("tensors", "act", "slope", "fused", "no_xhat", "s2_absent")
 
     def __init__(self, act: int, slope: float = 0.0):
         # leaky ReLU (act 2): the conv returns the RAW gradient and only its sums are masked, so
         # the BN backward re-applies act' and another consumer's gradient can still be added
         self.tensors, self.act, self.slope, self.fused = None, act, float(slope), None
+        self.no_xhat = self.s2_absent = False
 
     def release(self):
         self.tensors = self.fused = None
@@ -345,12 +351,20 @@ class BN3Linear:
     buffer.  Everything else -- no fused hand-off (the network's last block), SyncBN, another
     activation -- runs the two backwards unchanged.  ``armed``: the conv accepted the hand-off (its
     shape fits and it kept what the linear path needs); the BN offers nothing otherwise.
-    ``DCP_BN3_LINEAR=0`` switches it off (A/B)."""
+    ``DCP_BN3_LINEAR=0`` switches it off (A/B).
 
-    __slots__ = ("payload", "armed")
+    ``a2`` / ``wb``: conv3's input and bf16 weight, references left by its forward (no copies).  With
+    them bn3's backward forms its own sum g xhat = invstd W3 (g^T a2 - S1 (x) colmean(a2)) row by row
+    (``bn_lin_s2``) on the compute stream before it returns -- bn3's dgamma IS that sum, and a gradient
+    hook may pack it as soon as the node returns -- so the dgrad epilogue that hands g over does not read
+    bn3's input (:class:`BNSource` ``no_xhat``).  G = g^T a2 and colsum(a2) travel on in the payload:
+    conv3's backward needs both and recomputes neither."""
+
+    __slots__ = ("payload", "armed", "a2", "wb")
 
     def __init__(self):
         self.payload, self.armed = None, False
+        self.a2 = self.wb = None
 
 
 _BN3_LINEAR = [os.environ.get("DCP_BN3_LINEAR", "1") != "0"]
@@ -428,6 +442,7 @@ class _Conv2d(Function):
         y, slabs = K(x).conv_fwd(x, wb, stride, pad, stats)
         if lin is not None:
             ctx.save_for_backward(x, wt, wb)  # (wb: the cached bf16 weight, no copy)
+            lin.a2, lin.wb = x, wb
         else:
             ctx.save_for_backward(x, wt)
         ctx.geo = (weight.shape[1], weight.shape[2], stride, pad)
@@ -447,11 +462,11 @@ class _Conv2d(Function):
             if pay is not None:
                 # the BN behind this conv handed over its masked output gradient instead of its input
                 # gradient (BN3Linear): both of this conv's gradients from it, in one op
-                g, scale, invstd, sums, count = pay
+                g, scale, invstd, sums, count, G, cs = pay
                 if g.data_ptr() != dy.data_ptr() or g.shape != dy.shape:
                     raise RuntimeError("conv2d backward: the BN hand-off's gradient buffer was replaced")
                 dx, dw = K(dy).conv1x1_bn_lin_bwd(g, x, wb, wt, scale, invstd, sums, count,
-                                                 ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+                                                 ctx.needs_input_grad[0], ctx.needs_input_grad[1], G, cs)
                 ctx.link = ctx.bnsrc = ctx.deposit = None
                 return (dx if ctx.needs_input_grad[0] else None, dw if ctx.needs_input_grad[1] else None,
                         None, None, None, None, None, None, None, None, None)
@@ -481,6 +496,9 @@ class _Conv2d(Function):
                 if mask is not None:
                     res = None  # the activation mask bits replace the residual read
                 a = add.compact.contiguous() if isinstance(add, StridedGrad) else add
+                if src.no_xhat and mask is not None and src.act == 1:
+                    y = None  # the BN forms sum g' xhat itself (BN3Linear): its input is not read here
+                    src.s2_absent = True
                 dx, sums = k.conv_dgrad_bn(dy, wt, pad, a, y, res, scale, shift, mean, invstd, src.act, mask,
                                            src.slope)
                 src.fused = (dx, sums)
@@ -769,9 +787,13 @@ class _BNAct(Function):
         k = K(dy)
         src, ctx.src = ctx.src, None
         fused = src.fused if src is not None else None
+        s2_absent = src is not None and src.s2_absent
         if src is not None:
             src.release()
         lin, ctx.lin = ctx.lin, None
+        a2 = wb = None
+        if lin is not None:
+            a2, wb, lin.a2, lin.wb = lin.a2, lin.wb, None, None
         want_dres = ctx.has_res and ctx.needs_input_grad[4]
         if cfg.iabn:
             y, beta = x, mean  # saved (y, beta) in place of (x, mean)
@@ -813,9 +835,18 @@ class _BNAct(Function):
                     and ctx.needs_input_grad[0] and _BN3_LINEAR[0]):
                 # the 1x1 conv that produced x takes g and the sums themselves (BN3Linear): no
                 # elementwise pass, no input gradient of this BN
-                lin.payload = (g, scale, invstd, sums, float(ctx.count))
+                G = cs = None
+                if s2_absent:
+                    # sum g xhat (this BN's dgamma) from conv3's operands, enqueued here: row 1 of the
+                    # sums is complete on this stream when the node returns
+                    G, cs = k.bn_lin_s2(g, a2, wb, invstd, sums, float(ctx.count))
+                lin.payload = (g, scale, invstd, sums, float(ctx.count), G, cs)
                 dx = g
             else:
+                if s2_absent:
+                    # the epilogue skipped sum g xhat for a linear path not taken after all (switched
+                    # off since the forward, no input gradient wanted): both sums from g and x
+                    local = sums = k.bn_bwd_reduce(g, x, None, scale, shift, mean, invstd, 0, cfg.slope)
                 dx, _ = k.bn_bwd_elemt(g, x, None, scale, shift, mean, invstd, sums, float(ctx.count), post_act,
                                        cfg.slope, False)
             dres = g if want_dres else None
@@ -1176,6 +1207,8 @@ def batch_norm_act(x, slabs, gamma, beta, run_mean, run_var, training_stats, mom
         src = BNSource(cfg.act, cfg.slope)
     if lin is not None and (not lin.armed or src is None or iabn or group is not None or not x.is_cuda):
         lin = None  # (no fused hand-off can reach this BN's backward)
+    if lin is not None and lin.a2 is not None and cfg.act == 1 and residual is not None and _BN3_LINEAR[0]:
+        src.no_xhat = True  # ReLU with mask bits, local training statistics: the consumer's epilogue skips x
     out = _BNAct.apply(x, slabs, gamma, beta, residual, run_mean, run_var, cfg, link, src, lin)
     if src is not None:
         out._dcp_bnsrc = src
