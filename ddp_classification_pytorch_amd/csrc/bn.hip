@@ -246,30 +246,6 @@ __device__ __forceinline__ Welford merge_slabs(const float* __restrict__ slabs, 
   return a;
 }
 
-// slabs [R][2][C] -> out [3][C] (R <= kDirectSlabs)
-__global__ void __launch_bounds__(64 * kMergeWaves) bn_slab_merge_kernel(const float* __restrict__ slabs, int R, int M,
-                                                                         int C, float* __restrict__ out) {
-  const Welford a = merge_slabs(slabs, R, M, C, blockIdx.x);
-  const int c = blockIdx.x * kSlabCh + (threadIdx.x & 63);
-  if (threadIdx.x < kSlabCh && c < C) {
-    out[c] = a.n;
-    out[C + c] = a.mean;
-    out[2 * C + c] = a.m2;
-  }
-}
-
-// partials [P][3][C] -> out [3][C]
-__global__ void __launch_bounds__(64 * kMergeWaves) bn_merge_kernel(const float* __restrict__ part, int P, int C,
-                                                       float* __restrict__ out) {
-  const Welford a = merge_partials(part, P, C, blockIdx.x);
-  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
-  if ((threadIdx.x >> 6) == 0 && c < C) {
-    out[c] = a.n;
-    out[C + c] = a.mean;
-    out[2 * C + c] = a.m2;
-  }
-}
-
 // first level of a two-level partial merge: chunk blockIdx.y of kPartialChunk partial rows ->
 // tmp [chunks][3][C].  One workgroup merging thousands of partials (the stem conv's 7,168 at batch
 // 1024) ran 143 us on one CU; chunks of 128 spread it over the chip.
@@ -329,30 +305,47 @@ __device__ __forceinline__ void finalize_channel(const Welford& a, int c, float 
 }
 
 // local BN (one rank): partials [P][3][C] -> mean, invstd, scale, shift in one launch
-// (bn_merge + bn_finalize with W = 1; bit-identical to the two-kernel path)
+// (bn_merge + bn_finalize with W = 1; bit-identical to the two-kernel path).
+// raw != nullptr: the merged (n, mean, M2) go to raw [3][C] and nothing is finalized -- the first half
+// of the two-kernel path (bn_stats) IS this kernel.  A separate merge kernel inlined its own copy of
+// Welford::merge, and the compiler contracted d * f + mean into an FMA in one copy and into a
+// multiply and a packed add in another: the two paths differed in the last bit.
 __global__ void __launch_bounds__(64 * kMergeWaves) bn_merge_finalize_kernel(
     const float* __restrict__ part, int P, int C, float eps, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ scale,
     float* __restrict__ shift, float* __restrict__ run_mean, float* __restrict__ run_var, float momentum, float iabn_eps,
-    float* __restrict__ rgamma) {
+    float* __restrict__ rgamma, float* __restrict__ raw) {
   const Welford m = merge_partials(part, P, C, blockIdx.x);
   const int c = blockIdx.x * 64 + (threadIdx.x & 63);
   if ((threadIdx.x >> 6) != 0 || c >= C) return;
+  if (raw) {
+    raw[c] = m.n;
+    raw[C + c] = m.mean;
+    raw[2 * C + c] = m.m2;
+    return;
+  }
   Welford a{0.f, 0.f, 0.f};
   a.merge(m.n, m.mean, m.m2);  // the W = 1 merge of bn_finalize_kernel
   finalize_channel(a, c, eps, gamma, beta, mean, invstd, scale, shift, run_mean, run_var, momentum, iabn_eps, rgamma);
 }
 
-// local BN from the conv slabs in one launch (R <= kDirectSlabs): merge + finalize; the same
-// merge order as bn_slab_merge_kernel, so SyncBN at world size 1 stays bit-identical
+// local BN from the conv slabs in one launch (R <= kDirectSlabs): merge + finalize.  raw != nullptr:
+// (n, mean, M2) to raw [3][C] instead (bn_stats: the same compiled merge, so SyncBN at world size 1
+// stays bit-identical)
 __global__ void __launch_bounds__(64 * kMergeWaves) bn_slab_finalize_kernel(
     const float* __restrict__ slabs, int R, int M, int C, float eps, const float* __restrict__ gamma,
     const float* __restrict__ beta, float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ scale,
     float* __restrict__ shift, float* __restrict__ run_mean, float* __restrict__ run_var, float momentum, float iabn_eps,
-    float* __restrict__ rgamma) {
+    float* __restrict__ rgamma, float* __restrict__ raw) {
   const Welford m = merge_slabs(slabs, R, M, C, blockIdx.x);
   const int c = blockIdx.x * kSlabCh + (threadIdx.x & 63);
   if (threadIdx.x >= kSlabCh || c >= C) return;
+  if (raw) {
+    raw[c] = m.n;
+    raw[C + c] = m.mean;
+    raw[2 * C + c] = m.m2;
+    return;
+  }
   Welford a{0.f, 0.f, 0.f};
   a.merge(m.n, m.mean, m.m2);  // the W = 1 merge of bn_finalize_kernel
   finalize_channel(a, c, eps, gamma, beta, mean, invstd, scale, shift, run_mean, run_var, momentum, iabn_eps, rgamma);
@@ -577,6 +570,10 @@ __global__ void __launch_bounds__(256) bn_act_fwd_kernel(const bf16* __restrict_
 // timeout sets sync[2] and is reported by the host), reads its coefficients coherently and runs
 // bn_act_fwd's math as 4 virtual 256-thread workgroups; the last workgroup through resets sync[0..1]
 // for the next launch (stream-ordered: graph-replay safe).
+// This kernel inlines its own copy of the merge, so its bit-identity with bn_slab_finalize /
+// bn_merge_finalize rests on the compiler contracting both copies alike; nothing enforces it but
+// tests/test_bn_exact_gpu.py, which compares them on every route (writing the FMAs out in
+// Welford::merge would enforce it, and would move the local-BN statistics by an ulp).
 struct FinActParams {
   const bf16* x;
   const bf16* res;
@@ -939,13 +936,14 @@ static int launch_stat_partials(const bf16* x, const float* slabs, int M, int C,
 // part: bn_stats_partials(...) x 3 x C scratch; out [3][C]
 void launch_bn_stats(const bf16* x, const float* slabs, int M, int C, float* part, float* out, hipStream_t s) {
   const int R = (M + 127) / 128;
+  float* const none = nullptr;
   if (slabs && R <= kDirectSlabs) {
-    hipLaunchKernelGGL(bn_slab_merge_kernel, dim3((C + kSlabCh - 1) / kSlabCh), dim3(64 * kMergeWaves), 0, s, slabs,
-                       R, M, C, out);
+    hipLaunchKernelGGL(bn_slab_finalize_kernel, dim3((C + kSlabCh - 1) / kSlabCh), dim3(64 * kMergeWaves), 0, s,
+                       slabs, R, M, C, 0.f, none, none, none, none, none, none, none, none, 0.f, -1.f, none, out);
     return;
   }
   const int P = launch_stat_partials(x, slabs, M, C, part, s);
-  hipLaunchKernelGGL(bn_merge_kernel, dim3((C + 63) / 64), dim3(64 * kMergeWaves), 0, s, part, P, C, out);
+  launch_bn_merge(part, P, C, out, s);
 }
 
 void launch_bn_stats_finalize(const bf16* x, const float* slabs, int M, int C, float* part, float eps,
@@ -956,23 +954,25 @@ void launch_bn_stats_finalize(const bf16* x, const float* slabs, int M, int C, f
   if (slabs && R <= kDirectSlabs) {
     hipLaunchKernelGGL(bn_slab_finalize_kernel, dim3((C + kSlabCh - 1) / kSlabCh), dim3(64 * kMergeWaves), 0, s,
                        slabs, R, M, C, eps, gamma, beta, mean, invstd, scale, shift, rm, rv, momentum, iabn_eps,
-                       rgamma);
+                       rgamma, (float*)nullptr);
     return;
   }
   const int P = launch_stat_partials(x, slabs, M, C, part, s);
   hipLaunchKernelGGL(bn_merge_finalize_kernel, dim3((C + 63) / 64), dim3(64 * kMergeWaves), 0, s, part, P, C, eps, gamma, beta,
-                     mean, invstd, scale, shift, rm, rv, momentum, iabn_eps, rgamma);
+                     mean, invstd, scale, shift, rm, rv, momentum, iabn_eps, rgamma, (float*)nullptr);
 }
 
 void launch_bn_merge(const float* part, int P, int C, float* out, hipStream_t s) {
-  hipLaunchKernelGGL(bn_merge_kernel, dim3((C + 63) / 64), dim3(64 * kMergeWaves), 0, s, part, P, C, out);
+  float* const none = nullptr;
+  hipLaunchKernelGGL(bn_merge_finalize_kernel, dim3((C + 63) / 64), dim3(64 * kMergeWaves), 0, s, part, P, C, 0.f, none,
+                     none, none, none, none, none, none, none, 0.f, -1.f, none, out);
 }
 
 void launch_bn_merge_finalize(const float* part, int P, int C, float eps, const float* gamma, const float* beta,
                               float* mean, float* invstd, float* scale, float* shift, float* rm, float* rv,
                               float momentum, hipStream_t s, float iabn_eps, float* rgamma) {
   hipLaunchKernelGGL(bn_merge_finalize_kernel, dim3((C + 63) / 64), dim3(64 * kMergeWaves), 0, s, part, P, C, eps,
-                     gamma, beta, mean, invstd, scale, shift, rm, rv, momentum, iabn_eps, rgamma);
+                     gamma, beta, mean, invstd, scale, shift, rm, rv, momentum, iabn_eps, rgamma, (float*)nullptr);
 }
 
 void launch_partial_sum(const float* part, int P, int K, float* out, hipStream_t s) {

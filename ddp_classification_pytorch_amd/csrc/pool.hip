@@ -216,8 +216,10 @@ __global__ void __launch_bounds__(256) maxpool_bn_bwd_kernel(const bf16* __restr
       red[1][threadIdx.x][q] = s2[q] * invstd[ch * 8 + q];
     }
     __syncthreads();
-    if ((int)threadIdx.x < cpr * 8 * 2) {
-      const int which = threadIdx.x / (cpr * 8), c = threadIdx.x % (cpr * 8);
+    // all 2 C outputs, strided over the 256 threads (2 C > 256 from 256 channels on); each output
+    // sums its row slots in the same fixed order whichever thread takes it
+    for (int o = threadIdx.x; o < cpr * 8 * 2; o += 256) {
+      const int which = o / (cpr * 8), c = o % (cpr * 8);
       const int cch = c >> 3, q = c & 7;
       float t = 0.f;
       for (int r = cch; r < 256; r += cpr) t += red[which][r][q];
