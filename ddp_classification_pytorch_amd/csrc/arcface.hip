@@ -30,6 +30,13 @@
 // accumulator layout (lane holds 4 consecutive rows of one column) is read as a 32-deep k-fragment
 // whose k order is a fixed permutation, and the A operand is loaded in the same permuted order.
 // Deterministic: every sum has a fixed order (no atomics).
+//
+// Widths: Dp = 128 / 256 / 512 (KS = Dp / 32 = 4 / 8 / 16).  At Dp = 512 the forward keeps 64-class
+// tiles (2 x 64 KB of LDS, one workgroup per CU); the two backward kernels stage 32-class (dX) /
+// 32-row (dW) tiles -- per buffer 32 KB row-major + 32 KB transposed, 128 KB double buffered -- so the
+// dcos tile is ONE 32-deep k-fragment, and run one wave per SIMD (128 accumulator + 64 fragment
+// registers per lane).  The dW kernel's per-row (label, t, dphi, lse) travels with each row tile
+// through the same DMA ring, so its LDS does not depend on the batch size.
 #include "common.cuh"
 #include "launchers.h"
 
@@ -37,7 +44,11 @@ namespace dcp {
 
 namespace {
 
-constexpr int kArcTile = 64;  // classes (rows) per staged tile
+constexpr int kArcTile = 64;  // classes (rows) per staged tile (32 in the Dp = 512 backward kernels)
+constexpr int kArcInfo = 1024;  // bytes of per-row info staged beside a dW row tile (64 rows x 16 B)
+
+// rows / classes per staged tile of the two backward kernels
+constexpr int arc_bwd_tile(int KS) { return KS == 16 ? 32 : kArcTile; }
 
 struct ArcParams {
   const bf16* xn;    // [Bp][Dp] normalised features (rows >= B zero)
@@ -47,6 +58,7 @@ struct ArcParams {
   const int64_t* labels;  // [B]
   const float* lab;  // [Bp][2]: target logit s * phi, d phi / d cos (0, 0 for an invalid row)
   const float* lse;  // [Bp] (backward)
+  const float* info; // [Bp][4] (label as float or -1, t, dphi, lse): the dW kernel's per-row operands
   const float* gout; // [1] upstream gradient of the mean loss (backward)
   float* part;       // split partials
   float scale;       // 1 / B (mean reduction)
@@ -80,12 +92,18 @@ __device__ __forceinline__ uint32_t tr_off(uint32_t d, uint32_t c, uint32_t h) {
   return d * 128u + ((c ^ (d & 7u)) << 4) + (h << 3);
 }
 
+// the same for a [Dp][32] tile (64-byte rows): the 4 rows d, d + 4, d + 8, d + 12 that share a 256-byte
+// bank window take 4 distinct chunks, so 16 consecutive rows at one chunk cover all 64 banks
+__device__ __forceinline__ uint32_t tr32_off(uint32_t d, uint32_t c, uint32_t h) {
+  return d * 64u + ((c ^ ((d >> 2) & 3u)) << 4) + (h << 3);
+}
+
 // LDS-DMA versions of the two stagings (one 16-byte global_load_lds per lane and instruction, the
 // lane's data landing at base + 16 lane: the swizzle is applied on the source side).  Untracked: the
 // caller waits vmcnt(0) + barrier before reading the tile.  4 waves share the tile.
-template <int DP>
+template <int DP, int TILE = kArcTile>
 __device__ __forceinline__ void dma_rm(char* T, const bf16* g, int r0, int w, int lane) {
-  constexpr int CPR = DP / 8, RPB = 64 / CPR, NI = kArcTile / RPB / 4;  // rows per 1 KB block; blocks per wave
+  constexpr int CPR = DP / 8, RPB = 64 / CPR, NI = TILE / RPB / 4;  // rows per 1 KB block; blocks per wave
 #pragma unroll
   for (int i = 0; i < NI; ++i) {
     const int blk = w * NI + i;
@@ -106,6 +124,18 @@ __device__ __forceinline__ void dma_tr(char* T, const bf16* g, int c0, int ld, i
   }
 }
 
+template <int DP>
+__device__ __forceinline__ void dma_tr32(char* T, const bf16* g, int c0, int ld, int w, int lane) {
+  constexpr int NI = DP / 16 / 4;  // 16 rows (64 B each) per 1 KB block
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int blk = w * NI + i;
+    const int d = blk * 16 + lane / 4, pos = lane % 4;
+    const int c = pos ^ ((d >> 2) & 3);
+    dma16(g + (size_t)d * ld + c0 + c * 8, T + blk * 1024);
+  }
+}
+
 // the 8 bf16 of a permuted 32-deep k-fragment from a transposed tile: k slots 8q..8q+3 <- columns
 // 32 kk + 4q .. +3, slots 8q+4..8q+7 <- columns 32 kk + 16 + 4q .. +3 (the accumulator layout of
 // two 16-wide MFMA results, read as one k-fragment)
@@ -113,6 +143,12 @@ __device__ __forceinline__ bf16x8 tr_frag(const char* T, uint32_t d, int kk, uin
   const uint32_t lo = 32u * kk + 4u * q, hi = lo + 16u;  // column indices (bf16)
   const bf16x4 a = *LDS_PTR(const bf16x4, T + tr_off(d, lo >> 3, (lo >> 2) & 1u));
   const bf16x4 b = *LDS_PTR(const bf16x4, T + tr_off(d, hi >> 3, (hi >> 2) & 1u));
+  return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+}
+// the same from a [Dp][32] tile, whose 32 columns are the one k-fragment
+__device__ __forceinline__ bf16x8 tr32_frag(const char* T, uint32_t d, uint32_t q) {
+  const bf16x4 a = *LDS_PTR(const bf16x4, T + tr32_off(d, q >> 1, q & 1u));       // columns 4 q .. + 3
+  const bf16x4 b = *LDS_PTR(const bf16x4, T + tr32_off(d, 2u + (q >> 1), q & 1u));  // 16 + 4 q .. + 3
   return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 
@@ -185,12 +221,15 @@ __global__ void __launch_bounds__(256) arc_label_kernel(const bf16* __restrict__
 
 // MODE 0: forward partials (max, scaled sum, rank count) per (split, row);
 // MODE 1: dxn partials [S][Bp][Dp].  Grid (Bp / 64, S); 4 waves x 16 rows.
+// KS = 16 (Dp = 512): LDS admits one workgroup per CU (128 KB), and MODE 1's 128 accumulator + 64
+// fragment registers one wave per SIMD; MODE 1 stages 32-class tiles there (arc_bwd_tile).
 template <int KS, int MODE>
-__global__ void __launch_bounds__(256, 2) arc_rows_kernel(const ArcParams p) {
+__global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) arc_rows_kernel(const ArcParams p) {
   constexpr int DP = KS * 32, DF = DP / 16;
+  constexpr int TILE = MODE == 1 ? arc_bwd_tile(KS) : kArcTile, NJ = TILE / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // two buffers of [64 classes][DP] swizzled (+ [DP][64 classes] for MODE 1), LDS-DMA double buffered
-  constexpr int BUF = kArcTile * DP * 2 * (MODE == 1 ? 2 : 1);
+  // two buffers of [TILE classes][DP] swizzled (+ [DP][TILE classes] for MODE 1), LDS-DMA double buffered
+  constexpr int BUF = TILE * DP * 2 * (MODE == 1 ? 2 : 1);
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t q = lane >> 4, l15 = lane & 15;
@@ -225,29 +264,34 @@ __global__ void __launch_bounds__(256, 2) arc_rows_kernel(const ArcParams p) {
 #pragma unroll
     for (int f = 0; f < DF; ++f) dacc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int ntiles = p.Cp / kArcTile;
+  const int ntiles = p.Cp / TILE;  // (p.tps counts tiles of this width)
   const int t0 = split * p.tps, t1 = min(ntiles, t0 + p.tps);
   auto stage = [&](int tile, int b) {
     char* Wb = smem + b * BUF;
-    dma_rm<DP>(Wb, p.wn, tile * kArcTile, w, lane);
-    if constexpr (MODE == 1) dma_tr<DP>(Wb + kArcTile * DP * 2, p.wnT, tile * kArcTile, p.Cp, w, lane);
+    dma_rm<DP, TILE>(Wb, p.wn, tile * TILE, w, lane);
+    if constexpr (MODE == 1) {
+      if constexpr (TILE == 32)
+        dma_tr32<DP>(Wb + TILE * DP * 2, p.wnT, tile * TILE, p.Cp, w, lane);
+      else
+        dma_tr<DP>(Wb + TILE * DP * 2, p.wnT, tile * TILE, p.Cp, w, lane);
+    }
   };
   if (t0 < t1) stage(t0, 0);
   for (int tile = t0; tile < t1; ++tile) {
-    const int c0 = tile * kArcTile, b = (tile - t0) & 1;
+    const int c0 = tile * TILE, b = (tile - t0) & 1;
     const char* Wt = smem + b * BUF;
-    const char* WT = Wt + kArcTile * DP * 2;
+    const char* WT = Wt + TILE * DP * 2;
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // this tile landed for every wave; the other buffer's reads are done
     asm volatile("" ::: "memory");
     if (tile + 1 < t1) stage(tile + 1, b ^ 1);
-    f32x4 acc[4];
+    f32x4 acc[NJ];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         const bf16x8 a = *LDS_PTR(const bf16x8, Wt + rm_off(16 * j + l15, ks * 4 + q, DP));
         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, xf[ks], acc[j], 0, 0, 0);
       }
@@ -275,9 +319,9 @@ __global__ void __launch_bounds__(256, 2) arc_rows_kernel(const ArcParams p) {
         run_m = m_new;
       }
     } else {
-      bf16x8 dfr[2];
+      bf16x8 dfr[NJ / 2];
 #pragma unroll
-      for (int j = 0; j < 4; ++j)
+      for (int j = 0; j < NJ; ++j)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int cls = c0 + 16 * j + 4 * (int)q + i;
@@ -289,10 +333,14 @@ __global__ void __launch_bounds__(256, 2) arc_rows_kernel(const ArcParams p) {
           dfr[j >> 1][(j & 1) * 4 + i] = f2bf(d);
         }
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk)
+      for (int kk = 0; kk < NJ / 2; ++kk)
 #pragma unroll
         for (int f = 0; f < DF; ++f) {
-          const bf16x8 a = tr_frag(WT, 16u * f + l15, kk, q);
+          bf16x8 a;
+          if constexpr (TILE == 32)
+            a = tr32_frag(WT, 16u * f + l15, q);
+          else
+            a = tr_frag(WT, 16u * f + l15, kk, q);
           dacc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, dfr[kk], dacc[f], 0, 0, 0);
         }
     }
@@ -389,20 +437,37 @@ __global__ void __launch_bounds__(256) arc_norm_bwd_kernel(const float* __restri
   }
 }
 
+// the dW kernel's per-row operands, one thread per padded row: info[r] = (label as float, or -1 for an
+// invalid or padding row; t; dphi; lse)
+__global__ void __launch_bounds__(256) arc_rowinfo_kernel(const int64_t* __restrict__ labels,
+                                                          const float* __restrict__ lab,
+                                                          const float* __restrict__ lse, int B, int Bp, int C,
+                                                          float* __restrict__ info) {
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r >= Bp) return;
+  const int y = r < B ? (int)labels[r] : -1;
+  const bool valid = y >= 0 && y < C;
+  *(f32x4*)(info + (size_t)r * 4) = f32x4{valid ? (float)y : -1.f, lab[2 * r], lab[2 * r + 1], lse[r]};
+}
+
 // dW: one workgroup per 64-class block over every row; 4 waves x 16 classes.  Writes
 // dw[c][:D] = inv_w[c] (dwn - wn <dwn, wn>) for c < C (fp32).
 // With p.S > 1 row splits (grid.y), each split writes its dwn partial to p.part [S][Cp][DP] instead
 // and arc_norm_bwd_kernel sums the splits and applies the normalisation backward (small C: the
 // 64-class blocks alone leave most CUs idle).
+// The per-row operands (label as float or -1, t, dphi, lse) arrive with each row tile: p.info [Bp][4]
+// (arc_rowinfo_kernel), 16 bytes per row through the same DMA ring, so LDS does not grow with B.
+// KS = 16 (Dp = 512): 32-row tiles, one wave per SIMD (see arc_rows_kernel).
 template <int KS>
-__global__ void __launch_bounds__(256, 2) arc_dw_kernel(const ArcParams p, const float* __restrict__ inv_w,
-                                                        int D, float* __restrict__ dw) {
+__global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) arc_dw_kernel(const ArcParams p,
+                                                                       const float* __restrict__ inv_w, int D,
+                                                                       float* __restrict__ dw) {
   constexpr int DP = KS * 32, DF = DP / 16;
+  constexpr int TILE = arc_bwd_tile(KS), NJ = TILE / 16;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  // two buffers of ([64 rows][DP] swizzled, [DP][64 rows]), LDS-DMA double buffered, then the
-  // per-row (label, t, dphi, lse) of every row, staged once
-  constexpr int BUF = kArcTile * DP * 2 * 2;
-  float* info = (float*)(smem + 2 * BUF);  // [Bp][4]
+  // two buffers of ([TILE rows][DP] swizzled, [DP][TILE rows], the rows' info [TILE][4] in a 1 KB
+  // slot), LDS-DMA double buffered
+  constexpr int TB = TILE * DP * 2 * 2, BUF = TB + kArcInfo;
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t q = lane >> 4, l15 = lane & 15;
@@ -414,47 +479,48 @@ __global__ void __launch_bounds__(256, 2) arc_dw_kernel(const ArcParams p, const
   f32x4 dacc[DF];
 #pragma unroll
   for (int f = 0; f < DF; ++f) dacc[f] = f32x4{0.f, 0.f, 0.f, 0.f};
-  for (int r = tid; r < p.Bp; r += 256) {
-    const int y = r < p.B ? (int)p.labels[r] : -1;
-    const bool valid = y >= 0 && y < p.C;
-    *LDS_PTR(f32x4, info + r * 4) = f32x4{valid ? (float)y : -1.f, p.lab[2 * r], p.lab[2 * r + 1], p.lse[r]};
-  }
   auto stage = [&](int r0, int b) {
     char* Xb = smem + b * BUF;
-    dma_rm<DP>(Xb, p.xn, r0, w, lane);
-    dma_tr<DP>(Xb + kArcTile * DP * 2, p.xnT, r0, p.Bp, w, lane);
+    dma_rm<DP, TILE>(Xb, p.xn, r0, w, lane);
+    if constexpr (TILE == 32)
+      dma_tr32<DP>(Xb + TILE * DP * 2, p.xnT, r0, p.Bp, w, lane);
+    else
+      dma_tr<DP>(Xb + TILE * DP * 2, p.xnT, r0, p.Bp, w, lane);
+    // the tile's info rows: one DMA of one wave (a 32-row tile lands twice in the 1 KB slot)
+    if (w == 0) dma16(p.info + (size_t)(r0 + (lane & (TILE - 1))) * 4, Xb + TB);
   };
   // this split's row tiles
-  const int nrt = p.Bp / kArcTile, rps = (nrt + p.S - 1) / p.S;
+  const int nrt = p.Bp / TILE, rps = (nrt + p.S - 1) / p.S;
   const int rt0 = blockIdx.y * rps, rt1 = min(nrt, rt0 + rps);
-  const int rbeg = rt0 * kArcTile, rend = rt1 * kArcTile;
+  const int rbeg = rt0 * TILE, rend = rt1 * TILE;
   if (rbeg < rend) stage(rbeg, 0);
-  for (int r0 = rbeg; r0 < rend; r0 += kArcTile) {
-    const int b = ((r0 - rbeg) / kArcTile) & 1;
+  for (int r0 = rbeg; r0 < rend; r0 += TILE) {
+    const int b = ((r0 - rbeg) / TILE) & 1;
     const char* Xt = smem + b * BUF;
-    const char* XT = Xt + kArcTile * DP * 2;
+    const char* XT = Xt + TILE * DP * 2;
+    const float* info = (const float*)(Xt + TB);  // [TILE][4]
     asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();  // this row tile landed for every wave; the other buffer is free
     asm volatile("" ::: "memory");
-    if (r0 + kArcTile < rend) stage(r0 + kArcTile, b ^ 1);
-    f32x4 acc[4];
+    if (r0 + TILE < rend) stage(r0 + TILE, b ^ 1);
+    f32x4 acc[NJ];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < NJ; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < NJ; ++j) {
         const bf16x8 a = *LDS_PTR(const bf16x8, Xt + rm_off(16 * j + l15, ks * 4 + q, DP));
         acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, wf[ks], acc[j], 0, 0, 0);
       }
     // lane: cos of rows r0 + 16 j + 4 q + i for class cls
-    bf16x8 dfr[2];
+    bf16x8 dfr[NJ / 2];
 #pragma unroll
-    for (int j = 0; j < 4; ++j)
+    for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int rl = 16 * j + 4 * (int)q + i;
-        const f32x4 in = *LDS_PTR(const f32x4, info + (r0 + rl) * 4);
+        const f32x4 in = *LDS_PTR(const f32x4, info + rl * 4);
         const bool lab_col = (float)cls == in[0];
         const float x = lab_col ? in[1] : p.s * acc[j][i];
         const float pr = __expf(x - in[3]);
@@ -463,10 +529,14 @@ __global__ void __launch_bounds__(256, 2) arc_dw_kernel(const ArcParams p, const
         dfr[j >> 1][(j & 1) * 4 + i] = f2bf(d);
       }
 #pragma unroll
-    for (int kk = 0; kk < 2; ++kk)
+    for (int kk = 0; kk < NJ / 2; ++kk)
 #pragma unroll
       for (int f = 0; f < DF; ++f) {
-        const bf16x8 a = tr_frag(XT, 16u * f + l15, kk, q);
+        bf16x8 a;
+        if constexpr (TILE == 32)
+          a = tr32_frag(XT, 16u * f + l15, q);
+        else
+          a = tr_frag(XT, 16u * f + l15, kk, q);
         dacc[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, dfr[kk], dacc[f], 0, 0, 0);
       }
   }
@@ -511,17 +581,19 @@ template <int KS>
 void set_lds(const void* f, size_t bytes) {
   (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
+bool arc_dp_ok(int Dp) { return Dp == 128 || Dp == 256 || Dp == 512; }
+constexpr size_t kArcLdsMax = 160 * 1024;  // one workgroup may take the whole CU's LDS
 }  // namespace
 
 bool launch_arcface_l2norm_t(const void* x, bool is_bf16, int R, int D, int Rp, int Dp, bf16* y, bf16* yT, float* inv,
                              float eps, hipStream_t st) {
-  if (Rp % 64 || Rp < R || D > Dp || !(Dp == 128 || Dp == 256)) return false;
+  if (Rp % 64 || Rp < R || D > Dp || !arc_dp_ok(Dp)) return false;
 #define ARC_NT(T_, DP_) \
   hipLaunchKernelGGL((arc_l2norm_t_kernel<T_, DP_>), dim3(Rp / 64), dim3(256), 0, st, (const T_*)x, R, D, Rp, y, yT, inv, eps);
   if (is_bf16) {
-    if (Dp == 128) { ARC_NT(bf16, 128) } else { ARC_NT(bf16, 256) }
+    if (Dp == 128) { ARC_NT(bf16, 128) } else if (Dp == 256) { ARC_NT(bf16, 256) } else { ARC_NT(bf16, 512) }
   } else {
-    if (Dp == 128) { ARC_NT(float, 128) } else { ARC_NT(float, 256) }
+    if (Dp == 128) { ARC_NT(float, 128) } else if (Dp == 256) { ARC_NT(float, 256) } else { ARC_NT(float, 512) }
   }
 #undef ARC_NT
   return true;
@@ -539,7 +611,7 @@ int arcface_fused_dx_splits(int Bp, int Cp) {
 bool launch_arcface_fused_fwd(const bf16* xn, const bf16* wn, const int64_t* labels, int B, int Bp, int C, int Cp,
                               int Dp, float s, float m, int easy, float* lab, float* part, float* loss, int* rank,
                               float* lse, hipStream_t st) {
-  if (Bp % 64 || Cp % kArcTile || !(Dp == 128 || Dp == 256)) return false;
+  if (Bp % 64 || Cp % kArcTile || !arc_dp_ok(Dp)) return false;
   const float cm = cosf(m), sm = sinf(m), th = cosf(3.14159265358979f - m), mm = sinf(3.14159265358979f - m) * m;
   hipLaunchKernelGGL(arc_label_kernel, dim3(Bp / 4), dim3(256), 0, st, xn, wn, labels, B, Bp, C, Dp, s, cm, sm, th, mm,
                      easy, lab);
@@ -549,11 +621,12 @@ bool launch_arcface_fused_fwd(const bf16* xn, const bf16* wn, const int64_t* lab
   p.S = arcface_fused_fwd_splits(Bp, Cp);
   p.tps = (Cp / kArcTile + p.S - 1) / p.S;
   const size_t lds = (size_t)kArcTile * Dp * 2 * 2;
+  if (lds > kArcLdsMax) return false;
   const dim3 grid(Bp / 64, p.S);
 #define ARC_FWD(KS_)                                                                                   \
   set_lds<KS_>((const void*)arc_rows_kernel<KS_, 0>, lds);                                            \
   hipLaunchKernelGGL((arc_rows_kernel<KS_, 0>), grid, dim3(256), lds, st, p);
-  if (Dp == 128) { ARC_FWD(4) } else { ARC_FWD(8) }
+  if (Dp == 128) { ARC_FWD(4) } else if (Dp == 256) { ARC_FWD(8) } else { ARC_FWD(16) }
 #undef ARC_FWD
   hipLaunchKernelGGL(arc_fwd_finalize_kernel, dim3(Bp / 4), dim3(256), 0, st, part, p.S, B, Bp, C, labels,
                      lab, loss, rank, lse);
@@ -564,18 +637,20 @@ bool launch_arcface_fused_dx(const bf16* xn, const bf16* wn, const bf16* wnT, co
                              int C, int Cp, int Dp, int D, float s, const float* lab, const float* lse,
                              const float* gout, float scale, const float* inv_x, float* part, void* dx, bool dx_bf16,
                              hipStream_t st) {
-  if (Bp % 64 || Cp % kArcTile || !(Dp == 128 || Dp == 256) || D > Dp) return false;
+  if (Bp % 64 || Cp % kArcTile || !arc_dp_ok(Dp) || D > Dp) return false;
   ArcParams p{};
   p.xn = xn; p.wn = wn; p.wnT = wnT; p.labels = labels; p.lab = lab; p.lse = lse; p.gout = gout; p.part = part;
   p.scale = scale; p.B = B; p.Bp = Bp; p.C = C; p.Cp = Cp; p.Dp = Dp; p.s = s;
   p.S = arcface_fused_dx_splits(Bp, Cp);
-  p.tps = (Cp / kArcTile + p.S - 1) / p.S;
-  const size_t lds = (size_t)kArcTile * Dp * 2 * 2 * 2;
+  const int tile = arc_bwd_tile(Dp / 32);  // the kernel's class tile: the splits count tiles of that width
+  p.tps = (Cp / tile + p.S - 1) / p.S;
+  const size_t lds = (size_t)tile * Dp * 2 * 2 * 2;
+  if (lds > kArcLdsMax) return false;
   const dim3 grid(Bp / 64, p.S);
 #define ARC_DX(KS_)                                                                                    \
   set_lds<KS_>((const void*)arc_rows_kernel<KS_, 1>, lds);                                            \
   hipLaunchKernelGGL((arc_rows_kernel<KS_, 1>), grid, dim3(256), lds, st, p);
-  if (Dp == 128) { ARC_DX(4) } else { ARC_DX(8) }
+  if (Dp == 128) { ARC_DX(4) } else if (Dp == 256) { ARC_DX(8) } else { ARC_DX(16) }
 #undef ARC_DX
   const size_t ss = (size_t)Bp * Dp;
   if (dx_bf16)
@@ -596,21 +671,24 @@ int arcface_fused_dw_splits(int Bp, int Cp) {
 
 bool launch_arcface_fused_dw(const bf16* xn, const bf16* xnT, const bf16* wn, const int64_t* labels, int B, int Bp,
                              int C, int Cp, int Dp, int D, float s, const float* lab, const float* lse,
-                             const float* gout, float scale, const float* inv_w, float* part, float* dw,
-                             hipStream_t st) {
-  if (Bp % 64 || Cp % kArcTile || !(Dp == 128 || Dp == 256) || D > Dp) return false;
+                             const float* gout, float scale, const float* inv_w, float* part, float* info,
+                             float* dw, hipStream_t st) {
+  if (Bp % 64 || Cp % kArcTile || !arc_dp_ok(Dp) || D > Dp) return false;
   ArcParams p{};
   p.xn = xn; p.xnT = xnT; p.wn = wn; p.labels = labels; p.lab = lab; p.lse = lse; p.gout = gout;
   p.scale = scale; p.B = B; p.Bp = Bp; p.C = C; p.Cp = Cp; p.Dp = Dp; p.s = s;
   p.S = arcface_fused_dw_splits(Bp, Cp);
   p.part = part;
-  if (p.S > 1 && part == nullptr) return false;
-  const size_t lds = (size_t)kArcTile * Dp * 2 * 2 * 2 + (size_t)Bp * 16;
-  if (lds > 160 * 1024) return false;
+  p.info = info;
+  if ((p.S > 1 && part == nullptr) || info == nullptr) return false;
+  // two staged row tiles, each with its rows' info: independent of the batch size
+  const size_t lds = 2 * ((size_t)arc_bwd_tile(Dp / 32) * Dp * 2 * 2 + kArcInfo);
+  if (lds > kArcLdsMax) return false;
+  hipLaunchKernelGGL(arc_rowinfo_kernel, dim3((Bp + 255) / 256), dim3(256), 0, st, labels, lab, lse, B, Bp, C, info);
 #define ARC_DW(KS_)                                                                                    \
   set_lds<KS_>((const void*)arc_dw_kernel<KS_>, lds);                                                 \
   hipLaunchKernelGGL((arc_dw_kernel<KS_>), dim3(Cp / 64, p.S), dim3(256), lds, st, p, inv_w, D, dw);
-  if (Dp == 128) { ARC_DW(4) } else { ARC_DW(8) }
+  if (Dp == 128) { ARC_DW(4) } else if (Dp == 256) { ARC_DW(8) } else { ARC_DW(16) }
 #undef ARC_DW
   if (p.S > 1)
     hipLaunchKernelGGL(arc_norm_bwd_kernel<float>, dim3(C), dim3(256), 0, st, part, p.S, (size_t)Cp * Dp, wn, Dp, D,

@@ -1921,7 +1921,7 @@ std::tuple<Tensor, Tensor, Tensor> arcface_l2norm_t(const Tensor& x, int64_t Rp,
   auto inv = at::empty({Rp}, f32_like(x));
   TORCH_CHECK(dcp::launch_arcface_l2norm_t(x.data_ptr(), x.scalar_type() == at::kBFloat16, R, D, (int)Rp, (int)Dp,
                                            bpm(y), bpm(yT), inv.data_ptr<float>(), (float)eps, cur_stream()),
-              "arcface_l2norm_t: Rp % 64, D <= Dp in {128, 256}");
+              "arcface_l2norm_t: Rp % 64, D <= Dp in {128, 256, 512}");
   return {y, yT, inv};
 }
 
@@ -1944,7 +1944,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> arcface_fused_fwd(const Tensor& xn, c
                                             (float)m, easy, lab.data_ptr<float>(), part.data_ptr<float>(),
                                             loss.data_ptr<float>(), rank.data_ptr<int>(), lse.data_ptr<float>(),
                                             cur_stream()),
-              "arcface_fused_fwd: unsupported shape (B, C padded to 64, D padded to 128 / 256)");
+              "arcface_fused_fwd: unsupported shape (B, C padded to 64, D padded to 128 / 256 / 512)");
   return {loss, rank, lse, lab};
 }
 
@@ -1964,7 +1964,7 @@ Tensor arcface_fused_dx(const Tensor& xn, const Tensor& wn, const Tensor& wnT, c
                                            (float)s, lab.data_ptr<float>(), lse.data_ptr<float>(), g.data_ptr<float>(),
                                            (float)scale, inv_x.data_ptr<float>(), part.data_ptr<float>(),
                                            dx.data_ptr(), out_bf16, cur_stream()),
-              "arcface_fused_dx: unsupported shape");
+              "arcface_fused_dx: unsupported shape (B, C padded to 64, D <= Dp in {128, 256, 512})");
   return dx;
 }
 
@@ -1980,11 +1980,12 @@ Tensor arcface_fused_dw(const Tensor& xn, const Tensor& xnT, const Tensor& wn, c
   auto dw = at::empty({C, D}, f32_like(xn));
   const int S = dcp::arcface_fused_dw_splits(Bp, Cp);
   auto part = at::empty({S > 1 ? (int64_t)S * Cp * Dp : 1}, f32_like(xn));
+  auto info = at::empty({(int64_t)Bp * 4}, f32_like(xn));  // per-row (label, t, dphi, lse), staged tile by tile
   TORCH_CHECK(dcp::launch_arcface_fused_dw(bp(xn), bp(xnT), bp(wn), labels.data_ptr<int64_t>(), B, Bp, C, Cp, Dp, D,
                                            (float)s, lab.data_ptr<float>(), lse.data_ptr<float>(), g.data_ptr<float>(),
                                            (float)scale, inv_w.data_ptr<float>(), part.data_ptr<float>(),
-                                           dw.data_ptr<float>(), cur_stream()),
-              "arcface_fused_dw: unsupported shape");
+                                           info.data_ptr<float>(), dw.data_ptr<float>(), cur_stream()),
+              "arcface_fused_dw: unsupported shape (B, C padded to 64, D <= Dp in {128, 256, 512})");
   return dw;
 }
 

@@ -330,8 +330,10 @@ bool conv1x1_ps_supported(int K, int Co, long M);
 bool launch_conv1x1_ps(const bf16* src, const bf16* wt, int ldw, bf16* dst, float* stats, const bf16* zero, int M,
                        int K, int Co, int ablate, int cw, hipStream_t st);
 // Fused ArcFace head (arcface.hip): no [B, C] tensor.  xn [Bp][Dp] / wn [Cp][Dp] normalised bf16
-// (zero padding rows), Bp % 64 == Cp % 64 == 0, Dp in {128, 256}, (128 + Bp / 64) KB of LDS for
-// the dW kernel at Dp = 256; false = unsupported shape.
+// (zero padding rows), Bp % 64 == Cp % 64 == 0, Dp in {128, 256, 512}, any batch size (the kernels'
+// LDS does not depend on it); false = unsupported shape.  The partial buffers follow the *_splits
+// functions: part [S][Bp][4] (fwd), [S][Bp][Dp] (dx), [S][Cp][Dp] (dw, S > 1); info [Bp][4] is the
+// dW kernel's per-row scratch.
 bool launch_arcface_l2norm_t(const void* x, bool is_bf16, int R, int D, int Rp, int Dp, bf16* y, bf16* yT, float* inv,
                              float eps, hipStream_t st);
 int arcface_fused_fwd_splits(int Bp, int Cp);
@@ -346,8 +348,8 @@ bool launch_arcface_fused_dx(const bf16* xn, const bf16* wn, const bf16* wnT, co
 int arcface_fused_dw_splits(int Bp, int Cp);
 bool launch_arcface_fused_dw(const bf16* xn, const bf16* xnT, const bf16* wn, const int64_t* labels, int B, int Bp,
                              int C, int Cp, int Dp, int D, float s, const float* lab, const float* lse,
-                             const float* gout, float scale, const float* inv_w, float* part, float* dw,
-                             hipStream_t st);
+                             const float* gout, float scale, const float* inv_w, float* part, float* info,
+                             float* dw, hipStream_t st);
 // SyncBN peer-memory exchange (peer.hip): gather (mode 0, dst [world][n]) or rank-ordered sum
 // (mode 1, dst [n]) of n floats through the IPC-mapped mailboxes `boxes` ([world] base addresses);
 // a rank missing for timeout_ms sets *err and poisons dst with NaN (this and every later exchange)

@@ -1730,14 +1730,15 @@ class _ArcFaceFused(Function):
     live in MFMA registers only -- forward streams the normalised class weights through an online
     log-sum-exp (loss, label rank, lse), backward recomputes each tile and feeds dcos straight into
     the dX / dW MFMAs (the normalisation backward fused into their epilogues).  The per-step
-    memory is O((B + C) * D), so 100k+ classes fit where the unfused path needs 4 B*C bytes."""
+    memory is O((B + C) * D), so 100k+ classes fit where the unfused path needs 4 B*C bytes.
+    Covers every D <= 512 (padded to :func:`arcface_fused_dp`) and every batch size."""
 
     @staticmethod
     def forward(ctx, x, weight, labels, s, m, easy):
         k = K(x)
         B, D = x.shape
         C = weight.shape[0]
-        Dp = 128 if D <= 128 else 256
+        Dp = arcface_fused_dp(D)
         Bp, Cp = round_up(B, 64), round_up(C, 64)
         # normalised operands and their transposes (the backward's MFMA A operands), one pass each
         xn, xnT, inv_x = k.arcface_l2norm_t(x.contiguous(), Bp, Dp, 1e-12)  # zero rows B..Bp
@@ -1771,18 +1772,28 @@ def arcface_fused_enabled() -> bool:
     return os.environ.get("DCP_ARCFACE_FUSED", "1") != "0"
 
 
+ARCFACE_FUSED_MAX_D = 512
+
+
+def arcface_fused_dp(D: int) -> int:
+    """The padded feature width the fused kernels are instantiated for (the one place that picks
+    it): 128 for D <= 128, 256 for D <= 256, else 512."""
+    if not 1 <= D <= ARCFACE_FUSED_MAX_D:
+        raise ValueError(f"the fused ArcFace head covers 1 <= D <= {ARCFACE_FUSED_MAX_D}, got D = {D}")
+    return 128 if D <= 128 else 256 if D <= 256 else 512
+
+
 def arcface_fused_supported(B: int, D: int) -> bool:
-    """Shapes the fused kernels cover: D <= 256 (padded to 128 / 256), and the dW kernel's LDS
-    (two staged row tiles of 2 x 16 KB x Dp / 128 plus 16 B per padded row) within 160 KB."""
-    if D > 256:
-        return False
-    Dp = 128 if D <= 128 else 256
-    return 4 * 64 * Dp * 2 + round_up(B, 64) * 16 <= 160 * 1024
+    """Shapes the fused kernels cover: every D <= 512 (padded to :func:`arcface_fused_dp`) at every
+    batch size B -- the kernels' LDS depends on the padded width alone (the dW kernel stages its
+    per-row operands tile by tile)."""
+    return 1 <= D <= ARCFACE_FUSED_MAX_D
 
 
 def arcface_loss(x, weight, labels, s=30.0, m=0.5, easy_margin=True, return_logits=False):
     """Returns (mean loss, rank of label, margin logits or empty).  On the GPU without
-    ``return_logits`` (training, the reference's loss) the fused head runs: no [B, C] tensor."""
+    ``return_logits`` (training, the reference's loss) the fused head runs for every D <= 512 and
+    every batch size: no [B, C] tensor (wider features take the unfused kernel path)."""
     if (x.is_cuda and not return_logits and x.dim() == 2 and arcface_fused_supported(x.shape[0], x.shape[1])
             and arcface_fused_enabled() and x.dtype in (torch.float32, torch.bfloat16)):
         loss, rank = _ArcFaceFused.apply(x, weight, labels, float(s), float(m), bool(easy_margin))

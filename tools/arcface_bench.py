@@ -2,7 +2,10 @@
 """ArcFace head step time (forward + backward of ArcMarginProduct + CE on the features and the
 class weights), fused (csrc/arcface.hip) vs the unfused kernel path, and the peak extra memory.
 
-    python tools/arcface_bench.py [--batch 1024] [--classes 10000,100000] [--dim 256]
+    python tools/arcface_bench.py [--batch 1024[,8192]] [--classes 10000,100000] [--dim 256]
+
+Each row names the autograd function that ran in the "fused" arm (``_ArcFaceFused`` for every
+D <= 512 at every batch size; ``_ArcFace``, the unfused path, beyond) -- a silent fallback shows.
 """
 import argparse
 import os
@@ -19,11 +22,12 @@ def step(x, W, lab):
     x.grad = W.grad = None
     loss, _, _ = Fn.arcface_loss(x, W, lab, 30.0, 0.5, True)
     loss.backward()
+    return type(loss.grad_fn).__name__.replace("Backward", "")
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--batch", default="1024", help="batch size, or a comma-separated list of them")
     ap.add_argument("--classes", default="10000,100000")
     ap.add_argument("--dim", type=int, default=256)
     ap.add_argument("--iters", type=int, default=20)
@@ -34,18 +38,19 @@ def main():
     _ext.hip_ops()
     dev = torch.device("cuda", 0)
     print(f"{'B':>6s} {'C':>7s} {'D':>4s} | {'fused us':>9s} {'unfused us':>10s} {'speedup':>7s} | "
-          f"{'fused MB':>8s} {'unfused MB':>10s}")
-    for C in (int(c) for c in a.classes.split(",")):
+          f"{'fused MB':>8s} {'unfused MB':>10s} | path of the fused arm")
+    shapes = [(int(b), int(c)) for b in a.batch.split(",") for c in a.classes.split(",")]
+    for B, C in shapes:
         torch.manual_seed(0)
-        x = torch.randn(a.batch, a.dim, device=dev).requires_grad_(True)
+        x = torch.randn(B, a.dim, device=dev).requires_grad_(True)
         W = (torch.randn(C, a.dim, device=dev) * 0.05).requires_grad_(True)
-        lab = torch.randint(0, C, (a.batch,), device=dev)
-        res = {}
+        lab = torch.randint(0, C, (B,), device=dev)
+        res, path = {}, {}
         modes = {"both": ("1", "0"), "fused": ("1",), "unfused": ("0",)}[a.mode]
         for fused in modes:
             os.environ["DCP_ARCFACE_FUSED"] = fused
             for _ in range(3):
-                step(x, W, lab)
+                path[fused] = step(x, W, lab)
             torch.cuda.synchronize()
             torch.cuda.reset_peak_memory_stats()
             base = torch.cuda.memory_allocated()
@@ -76,8 +81,8 @@ def main():
             res[fused] = (e0.elapsed_time(e1) / a.iters * 1e3, peak)
         os.environ.pop("DCP_ARCFACE_FUSED", None)
         f, u = res.get("1", (float("nan"), 0.0)), res.get("0", (float("nan"), 0.0))
-        print(f"{a.batch:6d} {C:7d} {a.dim:4d} | {f[0]:9.1f} {u[0]:10.1f} {u[0] / f[0]:7.2f} | {f[1]:8.1f} {u[1]:10.1f}",
-              flush=True)
+        print(f"{B:6d} {C:7d} {a.dim:4d} | {f[0]:9.1f} {u[0]:10.1f} {u[0] / f[0]:7.2f} | {f[1]:8.1f} {u[1]:10.1f} | "
+              f"{path.get('1', '-')}", flush=True)
 
 
 if __name__ == "__main__":
