@@ -42,7 +42,8 @@ def run(args):
     net = wrap_ddp(model, rt.local_rank, syncbn=args.syncbn and (rt.world > 1 or args.force_ddp), bucket_cap_mb=args.bucket_cap_mb,
                    first_bucket_mb=args.first_bucket_mb, force=args.force_ddp)
     opt = build_optimizer(args.optimizer, model.parameters(), args.lr, args.momentum, args.weight_decay,
-                          args.nesterov)
+                          args.nesterov, lars_eta=getattr(args, "lars_eta", 1e-3),
+                          lars_eps=getattr(args, "lars_eps", 1e-8), lars_keep_1d=getattr(args, "lars_keep_1d", False))
     attach_optimizer(net, opt)  # multi-GPU: the step runs per gradient bucket behind its all-reduce
     sched = StepLR(opt, step_size=args.step_size, gamma=args.gamma)
     C = args.num_classes

@@ -92,8 +92,16 @@ def build_parser() -> argparse.ArgumentParser:
     a("--lr", type=float, default=None)
     a("--momentum", type=float, default=None)
     a("--weight-decay", "--weight_decay", "--weightDecay", dest="weight_decay", type=float, default=None)
-    a("--optimizer", default=None, help="SGD | Adam | AdamW")
+    a("--optimizer", default=None, help="SGD | Adam | AdamW | LARS")
     a("--nesterov", action="store_true")
+    a("--lars-eta", dest="lars_eta", type=float, default=1e-3, help="LARS trust coefficient")
+    a("--lars-eps", dest="lars_eps", type=float, default=1e-8, help="added to the trust ratio's denominator")
+    a("--lars-keep-1d", dest="lars_keep_1d", action="store_true",
+      help="LARS: adapt (and decay) BN scales / shifts and biases too, instead of stepping them with plain "
+           "momentum SGD without weight decay")
+    a("--lr-decay", dest="lr_decay", default="none", choices=["none", "poly"],
+      help="poly: after --warmup-iters, lr = target * (1 - (step - warm) / (total - warm))^2 per iteration, in "
+           "place of the per-epoch scheduler")
     a("--step-size", dest="step_size", type=int, default=None)
     a("--gamma", type=float, default=None)
     a("--lrSchedule", "--milestones", dest="milestones", type=int, nargs="+", default=None)

@@ -2011,6 +2011,52 @@ void mt_sgd(const Tensor& table, const Tensor& chunks, double lr, double momentu
                      reinterpret_cast<const int2*>(chunks.data_ptr()), chunks.size(0), h, cur_stream());
 }
 
+// LARS.  spans int32 [n,2] = (first chunk, chunk count) per table row; partials float [k,2] and
+// trust float [n] are the launch's scratch (trust holds the step's ratios afterwards).  Without
+// spans / partials / trust the group is not adaptive: one launch, every ratio 1.  lr_dev (optional
+// float32[1] on the device): the learning rate, read by the kernel -- a HIP-graph replay follows a
+// per-iteration schedule without recapture.
+void mt_lars(const Tensor& table, const Tensor& chunks, const c10::optional<Tensor>& spans,
+             const c10::optional<Tensor>& partials, const c10::optional<Tensor>& trust, double lr, double momentum,
+             double dampening, double wd, bool nesterov, bool first, double grad_scale, double eta, double eps,
+             const c10::optional<Tensor>& lr_dev) {
+  CHECK_DEV(table);
+  CHECK_DEV(chunks);
+  dcp::LarsHyper h;
+  h.sgd = dcp::SgdHyper{(float)lr, (float)momentum, (float)dampening, (float)wd, (float)grad_scale, nesterov ? 1 : 0,
+                        first ? 1 : 0};
+  h.trust = nullptr;
+  h.lr_dev = nullptr;
+  if (lr_dev.has_value() && lr_dev->defined()) {
+    CHECK_DEV((*lr_dev));
+    TORCH_CHECK(lr_dev->scalar_type() == at::kFloat && lr_dev->numel() == 1, "mt_lars: lr_dev float32[1]");
+    h.lr_dev = lr_dev->data_ptr<float>();
+  }
+  const int2* sp = nullptr;
+  float2* part = nullptr;
+  float* tr = nullptr;
+  const int64_t n = table.size(0), k = chunks.size(0);
+  if (trust.has_value() && trust->defined()) {
+    TORCH_CHECK(spans.has_value() && spans->defined() && partials.has_value() && partials->defined(),
+                "mt_lars: an adaptive step needs spans, partials and trust");
+    CHECK_DEV((*spans));
+    CHECK_DEV((*partials));
+    CHECK_DEV((*trust));
+    TORCH_CHECK(spans->scalar_type() == at::kInt && spans->is_contiguous() && spans->numel() == 2 * n,
+                "mt_lars: spans int32 [n,2]");
+    TORCH_CHECK(partials->scalar_type() == at::kFloat && partials->is_contiguous() && partials->numel() >= 2 * k,
+                "mt_lars: partials float [k,2]");
+    TORCH_CHECK(trust->scalar_type() == at::kFloat && trust->is_contiguous() && trust->numel() >= n,
+                "mt_lars: trust float [n]");
+    sp = reinterpret_cast<const int2*>(spans->data_ptr());
+    part = reinterpret_cast<float2*>(partials->data_ptr());
+    tr = trust->data_ptr<float>();
+  }
+  dcp::launch_mt_lars(reinterpret_cast<const dcp::MTEntry*>(table.data_ptr()),
+                      reinterpret_cast<const int2*>(chunks.data_ptr()), (int)k, sp, (int)n, part, tr, (float)eta,
+                      (float)eps, h, cur_stream());
+}
+
 // step_dev (optional int32[1] on the device): the step count the bias corrections use, read by
 // the kernel -- a HIP-graph replay then applies the current step's correction, not the captured one
 void mt_adam(const Tensor& table, const Tensor& chunks, double lr, double beta1, double beta2, double eps, double wd,
@@ -2292,6 +2338,11 @@ TORCH_LIBRARY(dcp, m) {
       "mt_adam(Tensor table, Tensor chunks, float lr, float beta1, float beta2, float eps, float wd, int step, bool "
       "decoupled, float grad_scale, Tensor? step_dev=None) -> ()",
       &mt_adam);
+  m.def(
+      "mt_lars(Tensor table, Tensor chunks, Tensor? spans, Tensor? partials, Tensor? trust, float lr, float momentum, "
+      "float dampening, float wd, bool nesterov, bool first, float grad_scale, float eta, float eps, Tensor? "
+      "lr_dev=None) -> ()",
+      &mt_lars);
   m.def("cdr_threshold(Tensor table, Tensor chunks, Tensor state) -> Tensor", &cdr_threshold);
   m.def("mt_copy(Tensor table, Tensor chunks, float scale, int mode) -> ()", &mt_copy);
   m.def(

@@ -265,10 +265,20 @@ struct AdamHyper {
   int decoupled;
   const int* step_dev;  // optional device step count: bc1/bc2 computed in-kernel from it
 };
+struct LarsHyper {
+  SgdHyper sgd;         // wd and grad_scale enter the scaled gradient d; the SGD update on d has no decay
+  const float* trust;   // per table entry, or null: every trust ratio is 1 (a non-adaptive group)
+  const float* lr_dev;  // optional device learning rate, read by the kernel instead of sgd.lr
+};
 // mode: bit 0 = source bf16, bit 1 = destination bf16 (MTEntry.p = destination, .g = source)
 void launch_mt_copy(const MTEntry* tab, const int2* chunks, int nchunks, float scale, int mode, hipStream_t s);
 void launch_mt_sgd(const MTEntry* tab, const int2* chunks, int nchunks, SgdHyper h, hipStream_t s);
 void launch_mt_adam(const MTEntry* tab, const int2* chunks, int nchunks, AdamHyper h, hipStream_t s);
+// LARS step: per-chunk sums of squares into partials [nchunks], per-tensor trust ratios (spans
+// [ntensors] = (first chunk, chunk count)) into trust [ntensors], then the update.  trust == null:
+// the two norm launches are skipped and every ratio is 1.
+void launch_mt_lars(const MTEntry* tab, const int2* chunks, int nchunks, const int2* spans, int ntensors,
+                    float2* partials, float* trust, float eta, float eps, LarsHyper h, hipStream_t s);
 void launch_cdr_threshold(const MTEntry* tab, const int2* chunks, int nchunks, uint32_t* state, uint32_t* hist,
                           hipStream_t s);
 void launch_cdr_mask(const MTEntry* tab, const int2* chunks, int nchunks, const uint32_t* state, float clip,

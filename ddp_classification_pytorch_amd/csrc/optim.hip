@@ -9,6 +9,9 @@
 //   workgroups to 4096-element slices.  The step optionally refreshes the
 //   bf16 compute copy of each weight, so the forward pass reads weights that
 //   the optimizer already converted.
+// * LARS over the same tables: per-chunk sums of squares, a per-tensor trust ratio, the SGD update on
+//   the scaled gradient; the learning rate optionally from a device scalar (HIP-graph replay under
+//   a per-iteration schedule).
 // * CDR (CDR/main.py:186-204): threshold = k-th largest |g*w| over all 2-D/4-D
 //   parameters, found by a 4-pass 8-bit radix select over the float bit
 //   patterns (non-negative floats order like their uint32 bits) without
@@ -78,6 +81,160 @@ __global__ void __launch_bounds__(256) mt_sgd_kernel(const MTEntry* __restrict__
     float p = e.p[i];
     float b = (h.momentum != 0.f && !h.first) ? e.s1[i] : 0.f;
     sgd_elem(e.g[i], p, b, h);
+    if (h.momentum != 0.f) e.s1[i] = b;
+    e.p[i] = p;
+    if (e.shadow) e.shadow[i] = f2bf(p);
+  }
+}
+
+
+// ---------------------------------------------------------------------------
+// LARS (layer-wise adaptive rate scaling; You, Gitman, Ginsburg 2017), "scaled gradient into SGD":
+//   g~ = grad_scale g;  trust = eta |w| / (|g~| + wd |w| + eps)  (1 when not adaptive or a norm is 0);
+//   d = trust (g~ + wd w);  then the SGD momentum / nesterov update on d with no further decay.
+// Three launches per (group, first / not-first) subset: per-chunk sums of squares, the per-tensor
+// trust ratio, the update.  Every reduction has a fixed order (no float atomics): a step is
+// bit-reproducible, and the same values give the same trust ratio at any pointer alignment.
+// ---------------------------------------------------------------------------
+
+// One workgroup per chunk: partials[blockIdx.x] = (sum w^2, sum g^2) of the chunk.  Thread t owns
+// the chunk elements 4 (t + 256 k) + u, k, u = 0..3, and accumulates them in that order with one
+// fused multiply-add each; then the wave butterfly and the serial sum over the four waves
+// (block_sum).  The 16-byte path loads the same four elements as one float4, so both paths add the
+// same values in the same order.
+__global__ void __launch_bounds__(256) mt_norm2_kernel(const MTEntry* __restrict__ tab, const int2* __restrict__ chunks,
+                                                       float2* __restrict__ partials) {
+  __shared__ float red[2][16];
+  const int2 ck = chunks[blockIdx.x];
+  const MTEntry e = tab[ck.x];
+  const int64_t base = (int64_t)ck.y * kChunk;
+  const int len = (int)(min(e.n, base + kChunk) - base);
+  const float* p = e.p + base;
+  const float* g = e.g + base;
+  float sw = 0.f, sg = 0.f;
+  const uintptr_t mis = ((uintptr_t)p | (uintptr_t)g) & 15u;
+  if (mis == 0 && (len & 3) == 0) {
+    const int n4 = len >> 2;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int j = threadIdx.x + 256 * k;
+      if (j < n4) {
+        float pv[4], gv[4];
+        *(float4*)pv = ((const float4*)p)[j];
+        *(float4*)gv = ((const float4*)g)[j];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          sw = fmaf(pv[u], pv[u], sw);
+          sg = fmaf(gv[u], gv[u], sg);
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i0 = 4 * (threadIdx.x + 256 * k);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (i0 + u < len) {
+          const float pv = p[i0 + u], gv = g[i0 + u];
+          sw = fmaf(pv, pv, sw);
+          sg = fmaf(gv, gv, sg);
+        }
+      }
+    }
+  }
+  sw = block_sum(sw, red[0]);
+  sg = block_sum(sg, red[1]);
+  if (threadIdx.x == 0) partials[blockIdx.x] = make_float2(sw, sg);
+}
+
+// One workgroup per tensor: its chunk partials summed in fp64 in a fixed order (thread t takes
+// partials t, t + 256, ... serially, then a shared-memory tree), so the merge adds no rounding of
+// its own; |w| and |grad_scale| |g| are rounded to fp32 once and the ratio is formed in fp32.
+__global__ void __launch_bounds__(256) lars_trust_kernel(const int2* __restrict__ spans, const float2* __restrict__ partials,
+                                                         float grad_scale, float wd, float eta, float eps,
+                                                         float* __restrict__ trust) {
+  __shared__ double sh[2][256];
+  const int2 sp = spans[blockIdx.x];  // (first chunk, number of chunks)
+  double aw = 0.0, ag = 0.0;
+  for (int c = threadIdx.x; c < sp.y; c += 256) {
+    const float2 v = partials[sp.x + c];
+    aw += (double)v.x;
+    ag += (double)v.y;
+  }
+  sh[0][threadIdx.x] = aw;
+  sh[1][threadIdx.x] = ag;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) {
+      sh[0][threadIdx.x] += sh[0][threadIdx.x + o];
+      sh[1][threadIdx.x] += sh[1][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float wn = (float)sqrt(sh[0][0]);
+    const float gn = (float)(fabs((double)grad_scale) * sqrt(sh[1][0]));
+    float t = 1.f;
+    if (wn > 0.f && gn > 0.f) t = eta * wn / (fmaf(wd, wn, gn) + eps);
+    trust[blockIdx.x] = t;
+  }
+}
+
+// mt_sgd_kernel's two loops with d = trust * (grad_scale g + wd p) in front of sgd_elem (which then
+// runs with wd = 0, grad_scale = 1: d * 1 is exact, so a trust ratio of 1 steps exactly as mt_sgd
+// does).  The learning rate comes from the device scalar when one is given: a replayed HIP graph
+// then follows a per-iteration schedule without recapture.
+__device__ __forceinline__ float lars_dir(float g, float p, float trust, float gs, float wd) {
+  float d = g * gs;
+  if (wd != 0.f) d = fmaf(wd, p, d);
+  return trust * d;
+}
+
+__global__ void __launch_bounds__(256) mt_lars_kernel(const MTEntry* __restrict__ tab, const int2* __restrict__ chunks,
+                                                      LarsHyper lh) {
+  const int2 ck = chunks[blockIdx.x];
+  const MTEntry e = tab[ck.x];
+  const int64_t base = (int64_t)ck.y * kChunk;
+  const int64_t end = min(e.n, base + kChunk);
+  SgdHyper h = lh.sgd;
+  const float gs = h.grad_scale, wd = h.wd;
+  h.grad_scale = 1.f;
+  h.wd = 0.f;
+  if (lh.lr_dev) h.lr = *lh.lr_dev;
+  const float trust = lh.trust ? lh.trust[ck.x] : 1.f;
+  const uintptr_t mis = ((uintptr_t)(e.p + base) | (uintptr_t)(e.g + base) |
+                         (h.momentum != 0.f ? (uintptr_t)(e.s1 + base) : 0)) & 15u;
+  const uintptr_t smis = e.shadow ? ((uintptr_t)(e.shadow + base) & 7u) : 0;
+  if (mis == 0 && smis == 0 && ((end - base) & 3) == 0) {
+    const int64_t n4 = (end - base) >> 2;
+    float4* p4 = (float4*)(e.p + base);
+    const float4* g4 = (const float4*)(e.g + base);
+    float4* s4 = (float4*)(e.s1 + base);
+#pragma unroll 4
+    for (int64_t j = threadIdx.x; j < n4; j += blockDim.x) {
+      float gv[4], pv[4], bv[4];
+      *(float4*)gv = g4[j];
+      *(float4*)pv = p4[j];
+      const bool mom = h.momentum != 0.f;
+      if (mom && !h.first) *(float4*)bv = s4[j];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) sgd_elem(lars_dir(gv[u], pv[u], trust, gs, wd), pv[u], bv[u], h);
+      if (mom) s4[j] = *(float4*)bv;
+      p4[j] = *(float4*)pv;
+      if (e.shadow) {
+        bf16x4 sv;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sv[u] = f2bf(pv[u]);
+        *(bf16x4*)(e.shadow + base + 4 * j) = sv;
+      }
+    }
+    return;
+  }
+  for (int64_t i = base + threadIdx.x; i < end; i += blockDim.x) {
+    float p = e.p[i];
+    float b = (h.momentum != 0.f && !h.first) ? e.s1[i] : 0.f;
+    sgd_elem(lars_dir(e.g[i], p, trust, gs, wd), p, b, h);
     if (h.momentum != 0.f) e.s1[i] = b;
     e.p[i] = p;
     if (e.shadow) e.shadow[i] = f2bf(p);
@@ -212,6 +369,17 @@ void launch_mt_copy(const MTEntry* tab, const int2* chunks, int nchunks, float s
 
 void launch_mt_sgd(const MTEntry* tab, const int2* chunks, int nchunks, SgdHyper h, hipStream_t s) {
   if (nchunks) hipLaunchKernelGGL(mt_sgd_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, h);
+}
+void launch_mt_lars(const MTEntry* tab, const int2* chunks, int nchunks, const int2* spans, int ntensors,
+                    float2* partials, float* trust, float eta, float eps, LarsHyper h, hipStream_t s) {
+  if (!nchunks) return;
+  if (trust) {  // adaptive: the update reads the trust ratios this step's norms give
+    hipLaunchKernelGGL(mt_norm2_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, partials);
+    hipLaunchKernelGGL(lars_trust_kernel, dim3(ntensors), dim3(256), 0, s, spans, partials, h.sgd.grad_scale,
+                       h.sgd.wd, eta, eps, trust);
+  }
+  h.trust = trust;
+  hipLaunchKernelGGL(mt_lars_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, h);
 }
 void launch_mt_adam(const MTEntry* tab, const int2* chunks, int nchunks, AdamHyper h, hipStream_t s) {
   if (nchunks) hipLaunchKernelGGL(mt_adam_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, h);

@@ -16,6 +16,10 @@ Differences from the reference, all deliberate:
 * ``--warmup-iters`` ramps the learning rate linearly per iteration from 1e-6
   (BASELINE ``WarmUp``, BASELINE/main.py:170-197; dead code in the reference,
   wired here for every workload that goes through this loop);
+* ``--lr-decay poly`` decays the learning rate per iteration after the warm-up (PolyDecay, a pure
+  function of the global step) in place of the per-epoch scheduler; an optimizer with a device
+  learning rate (FusedLARS: ``push_lr``) replays one captured HIP graph through warm-up and decay,
+  every other optimizer runs such steps eagerly as before;
 * GPU step time from HIP events (``gpu_ms_per_step`` in the JSONL log, no host
   sync beyond the log interval's), a per-rank heartbeat file
   (``heartbeat_rank<r>.txt``: wall time, step, loss every ``--heartbeat-every``
@@ -32,7 +36,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import functional as Fn
-from ..optim.schedulers import LinearWarmup
+from ..optim.schedulers import LinearWarmup, PolyDecay
 from .checkpoint import load_checkpoint, save_checkpoint
 from .logger import MetricsLogger
 
@@ -81,6 +85,12 @@ class ClassificationLoop:
         self.start_epoch, self.global_step, self.best = 0, 0, -1.0
         self.warmup = None
         self._warmup_state = None  # LinearWarmup.state_dict() from a resumed checkpoint
+        self.poly = None  # --lr-decay poly: built in the first epoch (needs the steps per epoch)
+        self._poly_on = getattr(args, "lr_decay", "none") == "poly"
+        if self._poly_on:
+            self.scheduler = None  # the per-iteration decay replaces the epoch scheduler for this run
+        # the optimizer's kernels read the learning rate from the device: a captured step follows it
+        self._dev_lr = hasattr(optimizer, "push_lr")
 
     # ------------------------------------------------------------------ persistence
     def _ckpt(self, name):
@@ -129,7 +139,8 @@ class ClassificationLoop:
     def _setup_graph(self):
         """--graph: single-process GPU runs replay the whole step as a HIP graph (engine/graph.py),
         recaptured at every epoch start (the learning rate is a captured kernel argument) and
-        after the LR warm-up (its steps run eagerly: the LR changes every iteration)."""
+        after the LR warm-up (its steps run eagerly: the LR changes every iteration).  An optimizer
+        with a device learning rate (``push_lr``) keeps one capture through all of that."""
         a = self.args
         self._grapher = None
         graph_safe = not any(isinstance(m, torch.nn.parallel.DistributedDataParallel) for m in self.train_modules)
@@ -145,15 +156,18 @@ class ClassificationLoop:
         optimizer, and ramping towards that would leave a resumed run below the uninterrupted one."""
         iters = int(getattr(self.args, "warmup_iters", 0) or 0)
         if iters > 0 and self.global_step < iters and self.warmup is None:
-            target = getattr(self.args, "lr", None)
-            if target is None and self.scheduler is not None and getattr(self.scheduler, "base_lrs", None):
-                target = self.scheduler.base_lrs[0]
-            if target is None:
-                target = self.optimizer.param_groups[0].get("initial_lr", self.optimizer.param_groups[0]["lr"])
-            self.warmup = LinearWarmup(self.optimizer, iters, float(target), start_lr=1e-6)
+            self.warmup = LinearWarmup(self.optimizer, iters, self._target_lr(), start_lr=1e-6)
             self.warmup.n = self.global_step  # resumed mid-warm-up: continue the ramp
             if self._warmup_state is not None and self._warmup_state.get("iters") == iters:
                 self.warmup.load_state_dict(self._warmup_state)
+
+    def _target_lr(self):
+        target = getattr(self.args, "lr", None)
+        if target is None and self.scheduler is not None and getattr(self.scheduler, "base_lrs", None):
+            target = self.scheduler.base_lrs[0]
+        if target is None:
+            target = self.optimizer.param_groups[0].get("initial_lr", self.optimizer.param_groups[0]["lr"])
+        return float(target)
 
     def _heartbeat(self, epoch):
         """Host-only (no device sync): wall time and step, so a stalled rank stops advancing."""
@@ -168,7 +182,7 @@ class ClassificationLoop:
         a, dev = self.args, self.rt.device
         if not hasattr(self, "_grapher"):
             self._setup_graph()
-        if self._grapher is not None:
+        if self._grapher is not None and not self._dev_lr:
             self._grapher.reset()  # the epoch's learning rate is baked into the captured step
         self._setup_warmup()
         prof = None
@@ -192,6 +206,9 @@ class ClassificationLoop:
         n_steps = len(self.train_data)
         if a.max_steps_per_epoch:
             n_steps = min(n_steps, a.max_steps_per_epoch)
+        if self._poly_on and self.poly is None:
+            self.poly = PolyDecay(self.optimizer, a.epochs * n_steps, self._target_lr(),
+                                  warm=int(getattr(a, "warmup_iters", 0) or 0))
         t0 = t_win = time.time()
         for i, batch in enumerate(self.train_data):
             if i >= n_steps:
@@ -203,11 +220,15 @@ class ClassificationLoop:
             in_warmup = self.warmup is not None and not self.warmup.done
             if in_warmup:
                 self.warmup.step()
-            if self._grapher is not None and not in_warmup:
+            elif self.poly is not None:
+                self.poly.set(self.global_step)
+            if self._dev_lr:
+                self.optimizer.push_lr()
+            if self._grapher is not None and (self._dev_lr or not (in_warmup or self.poly is not None)):
                 loss, rank = self._grapher(*batch)
             elif self._grapher is not None:
                 loss, rank = self._grapher.eager(*batch)  # the grapher's side stream, as its own warm-up
-                if self.warmup.done:
+                if in_warmup and self.warmup.done and self.poly is None:
                     self._grapher.reset()  # capture at the final warm-up learning rate
             else:
                 loss, rank = self._train_step(*batch)

@@ -18,6 +18,10 @@ counter that the captured step itself increments (``mt_adam(step_dev=...)``), an
 ``state_dict`` / resume see the true count.  SGD has no step-dependent argument; the
 learning rate of a captured step is the one at capture (the grapher recaptures when it
 changes).
+
+:class:`FusedLARS` (layer-wise adaptive rate scaling for large global batches) adds a per-tensor
+trust ratio in front of the SGD update (``mt_lars``) and reads its learning rate from a device
+scalar, so a captured step follows a per-iteration schedule without recapture.
 """
 from __future__ import annotations
 
@@ -304,3 +308,174 @@ class FusedAdam(torch.optim.Optimizer):
             st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
             denom = st["exp_avg_sq"].sqrt() / math.sqrt(bc2) + group["eps"]
             p.addcdiv_(st["exp_avg"], denom, value=-group["lr"] / bc1)
+
+
+class _LarsTables(_TableCache):
+    """A LARS launch's tables plus its scratch: the per-tensor (first chunk, chunk count) spans, the
+    per-chunk (sum w^2, sum g^2) partials and the per-tensor trust ratios.  Like the chunk list they
+    depend only on the tensor sizes.  One per launch key: the compute stream's ``step()`` and the
+    comm stream's per-bucket ``step_params()`` never share scratch."""
+
+    def __init__(self):
+        super().__init__()
+        self.span_sizes = None
+        self.spans = self.partials = self.trust = None
+
+    def get(self, entries, device):
+        super().get(entries, device)
+        if self.sizes != self.span_sizes:
+            counts = [(n + CHUNK - 1) // CHUNK for n in self.sizes]
+            firsts, acc = [], 0
+            for c in counts:
+                firsts.append(acc)
+                acc += c
+            self.spans = Fn.table_to_device([[f, c] for f, c in zip(firsts, counts)], torch.int32, device).view(-1, 2)
+            self.partials = torch.zeros(acc, 2, dtype=torch.float32, device=device)
+            self.trust = torch.ones(len(counts), dtype=torch.float32, device=device)
+            self.span_sizes = self.sizes
+        return self
+
+
+class FusedLARS(FusedSGD):
+    """Layer-wise adaptive rate scaling (You, Gitman, Ginsburg 2017) in front of FusedSGD's update:
+
+        g~    = grad_scale * g
+        trust = eta * |w| / (|g~| + wd * |w| + eps)    if adapt and |w| > 0 and |g~| > 0, else 1
+        d     = trust * (g~ + wd * w)
+        buf   = d  (a parameter's first gradient)  |  momentum * buf + (1 - dampening) * d
+        w    -= lr * (d + momentum * buf  if nesterov else  buf)
+
+    GPU: per (group, first / not-first) subset the ``mt_lars`` op launches the per-chunk sums of
+    squares, the per-tensor trust ratios (chunk partials merged in fp64 in a fixed order; no float
+    atomics, so a step is bit-reproducible) and the update.  The trust ratio never leaves the device.
+
+    Device learning rate: each group owns a ``float32[1]`` device tensor that the update kernel reads.
+    ``group["lr"]`` stays the host truth (schedulers, checkpoints, logging); :meth:`push_lr` writes
+    it to the device when it changed.  A HIP-graph replay therefore follows a per-iteration schedule
+    without recapture: change ``group["lr"]``, call ``push_lr()``, replay.
+    """
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
+                 grad_scale=1.0, eta=1e-3, eps=1e-8, adapt=True):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                        nesterov=nesterov, grad_scale=grad_scale, eta=eta, eps=eps, adapt=adapt)
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        self._tables = {}
+        self._fast = {}          # launch key -> (pointer fingerprint, _LarsTables)
+        self._gid = None
+        self._reducer_stepped = False
+        self._lr_dev = {}        # group index -> [float32[1] device tensor, host value last written]
+        self._trust = {}         # id(param) -> (trust tensor, index) of its last step
+        self._ones = {}          # device -> float32[1] of 1.0 (trust_of for non-adaptive groups)
+        self._via = "step"       # which entry point is stepping: part of the launch key
+
+    # ------------------------------------------------------------------ device learning rate
+    def push_lr(self):
+        """Write each group's ``lr`` into its device scalar on the current stream if the host value
+        changed since the last write; a no-op otherwise (and before the first GPU step, which creates
+        the scalars from the learning rates of that moment)."""
+        for gi, ent in self._lr_dev.items():
+            lr = float(self.param_groups[gi]["lr"])
+            if ent[1] != lr:
+                ent[0].fill_(lr)
+                ent[1] = lr
+
+    def _lr_tensor(self, gi, group, device):
+        ent = self._lr_dev.get(gi)
+        if ent is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedLARS: the device learning rate must be created by an eager step before "
+                                   "capture")
+            lr = float(group["lr"])
+            ent = self._lr_dev[gi] = [torch.full((1,), lr, dtype=torch.float32, device=device), lr]
+        return ent[0]
+
+    def trust_of(self, p):
+        """The trust ratio of ``p``'s last step as a device scalar view (no sync); 1 for a parameter
+        of a non-adaptive group, None before its first step."""
+        return self._trust.get(id(p))
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        for ent in self._lr_dev.values():
+            ent[1] = None  # the loaded learning rates are written at the next push
+
+    @staticmethod
+    def _capturing():
+        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if not self._capturing():
+            self.push_lr()
+        self._via = "step"
+        return super().step(closure)
+
+    @torch.no_grad()
+    def step_params(self, params):
+        if not self._capturing():
+            self.push_lr()
+        self._via = "bucket"
+        super().step_params(params)
+
+    def _update(self, gi, group, params, first):
+        mom, wd, gs = group["momentum"], group["weight_decay"], group["grad_scale"]
+        adapt = bool(group["adapt"])
+        if params[0].is_cuda:
+            dev = params[0].device
+            lr_dev = self._lr_tensor(gi, group, dev)
+            key = (self._via, gi, first, len(params), params[0].data_ptr())
+            fp = (adapt,) + tuple((p.data_ptr(), p.grad.data_ptr()) for p in params)
+            hit = self._fast.get(key) if not first else None
+            if hit is not None and hit[0] == fp:
+                tabs = hit[1]
+            else:
+                entries = []
+                for p in params:
+                    if not (p.is_contiguous() and p.grad.is_contiguous()):
+                        raise RuntimeError("FusedLARS needs contiguous params and grads")
+                    if p.dtype != torch.float32 or p.grad.dtype != torch.float32:
+                        raise RuntimeError("FusedLARS expects fp32 master params and grads")
+                    buf = self.state[p].get("momentum_buffer")
+                    entries.append((p.data_ptr(), p.grad.data_ptr(), buf.data_ptr() if buf is not None else 0, 0, 0,
+                                    p.numel()))
+                tabs = self._tables.setdefault(key, _LarsTables()).get(entries, dev)
+                if not first:
+                    self._fast[key] = (fp, tabs)
+                if adapt:
+                    for i, p in enumerate(params):
+                        self._trust[id(p)] = tabs.trust[i]
+                else:
+                    one = self._ones.get(dev)
+                    if one is None:
+                        one = self._ones[dev] = torch.ones((), dtype=torch.float32, device=dev)
+                    for p in params:
+                        self._trust[id(p)] = one
+            _ext.hip_ops().mt_lars(tabs.table, tabs.chunks, tabs.spans if adapt else None,
+                                   tabs.partials if adapt else None, tabs.trust if adapt else None, group["lr"], mom,
+                                   group["dampening"], wd, group["nesterov"], first, gs, group["eta"], group["eps"],
+                                   lr_dev)
+            return
+        # CPU: the same formulas in fp32 (norms merged in fp64, as the trust kernel does)
+        for p in params:
+            g = p.grad * gs
+            trust = torch.ones((), dtype=torch.float32)
+            if adapt:
+                wn = (p.detach() * p.detach()).sum(dtype=torch.float64).sqrt().float()
+                gn = ((p.grad * p.grad).sum(dtype=torch.float64).sqrt() * abs(gs)).float()
+                if wn > 0 and gn > 0:
+                    trust = group["eta"] * wn / (wd * wn + gn + group["eps"])
+            self._trust[id(p)] = trust
+            if wd:
+                g = g + wd * p
+            g = trust * g
+            if mom:
+                buf = self.state[p]["momentum_buffer"]
+                if first:
+                    buf.copy_(g)
+                else:
+                    buf.mul_(mom).add_(g, alpha=1 - group["dampening"])
+                g = g + mom * buf if group["nesterov"] else buf
+            p.add_(g, alpha=-group["lr"])

@@ -42,3 +42,32 @@ class LinearWarmup:
 
     def load_state_dict(self, sd):
         self.n, self.iters, self.target, self.start = sd["n"], sd["iters"], sd["target"], sd["start"]
+
+
+class PolyDecay:
+    """Per-iteration polynomial decay after the warm-up (the LARS large-batch recipe):
+
+        lr_at(step) = target * (1 - (step - warm) / (total - warm)) ** power      for step >= warm
+
+    with ``step`` the 0-based global iteration and ``total`` = epochs x steps per epoch.  Up to the
+    end of the warm-up (``step <= warm``, the ramp is :class:`LinearWarmup`'s) it returns the target;
+    past ``total`` it stays at 0.  A pure function of the step: resuming needs no state."""
+
+    def __init__(self, optimizers, total: int, target_lr: float, warm: int = 0, power: float = 2.0):
+        self.optimizers = optimizers if isinstance(optimizers, (list, tuple)) else [optimizers]
+        self.total, self.warm = int(total), max(0, int(warm))
+        self.target, self.power = float(target_lr), float(power)
+
+    def lr_at(self, step: int) -> float:
+        span = self.total - self.warm
+        if step <= self.warm or span <= 0:
+            return self.target
+        f = min(1.0, (step - self.warm) / float(span))
+        return self.target * (1.0 - f) ** self.power
+
+    def set(self, step: int) -> float:
+        lr = self.lr_at(step)
+        for opt in self.optimizers:
+            for g in opt.param_groups:
+                g["lr"] = lr
+        return lr
