@@ -15,10 +15,14 @@
 //     Resize+CenterCrop box of the eval transform) from a counter-based RNG keyed by
 //     (seed, epoch, dataset index), so results do not depend on thread scheduling;
 //   * the crop/resize/flip itself runs on the GPU (`dcp::crop_resize_kernel`) after one
-//     H2D copy of the raw records, feeding the existing normalise/NHWC input kernel.
+//     H2D copy of the raw records, feeding the existing normalise/NHWC input kernel;
+//   * presets that rotate or pad (CDR/main.py:112-130, NESTED/train.py:40-45 on CIFAR,
+//     PLC/FolderDataset.py) go through dcpl_submit_affine: the same gather and box, plus one
+//     inverse-affine matrix per image that composes resize-to-canvas, rotation about the canvas
+//     centre, flip and the crop offset, resampled on the GPU by `dcp::warp_crop_kernel`.
 //
 // C ABI (ctypes, see data/shards.py): dcpl_open / dcpl_close / dcpl_count / dcpl_pool_create /
-// dcpl_pool_destroy / dcpl_submit / dcpl_wait.
+// dcpl_pool_destroy / dcpl_submit / dcpl_submit_affine / dcpl_wait.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -76,13 +80,19 @@ struct Shard {
 };
 
 // Augmentation spec shared with Python (ctypes.Structure in data/shards.py).
+// The fields after flip_p are read by dcpl_submit_affine only; an 8-field initialiser leaves them
+// zero: no rotation, no padding, canvas = output.
 struct AugSpec {
-  int32_t mode;         // 0 = RandomResizedCrop (+flip), 1 = Resize(resize)+CenterCrop(crop), 2 = whole image
+  int32_t mode;         // 0 = RandomResizedCrop (+flip), 1 = Resize(resize)+CenterCrop(crop), 2 = whole image,
+                        // 3 = RandomCrop(out, padding=pad) of the image itself, 4 = whole image stretched to the canvas
   int32_t resize;       // mode 1: shorter side after resize
   int32_t crop;         // mode 1: centre crop edge (in resized pixels)
   float scale_lo, scale_hi;  // mode 0: area fraction range
   float ratio_lo, ratio_hi;  // mode 0: aspect ratio range
-  float flip_p;         // horizontal flip probability (modes 0 and 2)
+  float flip_p;         // horizontal flip probability (every mode but 1)
+  float rot_deg;        // RandomRotation(rot_deg) about the canvas centre; 0 = none
+  int32_t pad;          // mode 3: zero padding on every side
+  int32_t canvas_h, canvas_w;  // the box is resized to this canvas, the output is its centre crop; 0 = output size
 };
 
 // splitmix64 / counter-based stream: one independent stream per (seed, epoch, dataset index)
@@ -142,6 +152,25 @@ void center_box(int H, int W, const AugSpec& a, int out[4]) {
   int ch = std::min(H, static_cast<int>(std::lround(a.crop / s)));
   int cw = std::min(W, static_cast<int>(std::lround(a.crop / s)));
   out[0] = (H - ch) / 2, out[1] = (W - cw) / 2, out[2] = ch, out[3] = cw;
+}
+
+// The inverse map of "resize the h x w box to an Sh x Sw canvas, rotate by theta degrees about the
+// canvas centre (PIL Image.rotate: counter-clockwise, cos/sin rounded to 15 digits), flip, crop
+// out_w columns at offset (dx, dy)": output pixel (ox, oy) -> box-relative source position
+// (sx, sy) = (m[0]*ox + m[1]*oy + m[2], m[3]*ox + m[4]*oy + m[5]), box pixel k centred at k.
+void affine_matrix(int h, int w, int Sh, int Sw, int out_w, double dx, double dy, double theta, int flip,
+                   float m[6]) {
+  const double a = -theta * 3.14159265358979323846 / 180.0;
+  const double ca = std::round(std::cos(a) * 1e15) / 1e15, sa = std::round(std::sin(a) * 1e15) / 1e15;
+  const double cx = Sw / 2.0, cy = Sh / 2.0, kx = static_cast<double>(w) / Sw, ky = static_cast<double>(h) / Sh;
+  const double fs = flip ? -1.0 : 1.0, f0 = flip ? out_w - 1.0 : 0.0;
+  const double px0 = f0 + 0.5 + dx - cx, py0 = 0.5 + dy - cy;  // (px - cx, py - cy) at ox = oy = 0
+  m[0] = static_cast<float>(ca * fs * kx);
+  m[1] = static_cast<float>(sa * kx);
+  m[2] = static_cast<float>((cx + ca * px0 + sa * py0) * kx - 0.5);
+  m[3] = static_cast<float>(-sa * fs * ky);
+  m[4] = static_cast<float>(ca * ky);
+  m[5] = static_cast<float>((cy - sa * px0 + ca * py0) * ky - 0.5);
 }
 
 class Pool {
@@ -308,6 +337,57 @@ int64_t dcpl_submit(void* pool, void* shard, const int64_t* indices, int B, uint
     m[1] = H, m[2] = W, m[3] = box[0], m[4] = box[1], m[5] = box[2], m[6] = box[3], m[7] = flip;
     labels[b] = e.label;
     return 0;
+  });
+}
+
+// dcpl_submit for the presets that rotate, pad or resize to a canvas other than the output: the
+// same gather, meta and labels, plus xf[b*8 .. b*8+8) = {m00, m01, m02, m10, m11, m12, angle_deg, 0}
+// (affine_matrix above) for an out_h x out_w output.  Draws per image, from the same
+// (seed, epoch, index) stream: the mode's own, then the angle (only if rot_deg > 0), then the flip --
+// so a spec without rotation and padding writes the meta dcpl_submit writes.
+int64_t dcpl_submit_affine(void* pool, void* shard, const int64_t* indices, int B, uint8_t* out, int64_t out_cap,
+                           int64_t* meta, float* xf, int64_t* labels, const AugSpec* aug, uint64_t seed,
+                           uint64_t epoch, int out_h, int out_w) {
+  auto* s = static_cast<Shard*>(shard);
+  const uint64_t stride = s->hdr->max_bytes;
+  if (B < 0 || static_cast<uint64_t>(B) * stride > static_cast<uint64_t>(out_cap)) return -2;
+  for (int b = 0; b < B; ++b)
+    if (indices[b] < 0 || static_cast<uint64_t>(indices[b]) >= s->hdr->count) return -3;
+  AugSpec a = *aug;
+  if (out_h <= 0 || out_w <= 0 || a.mode < 0 || a.mode > 4 || a.pad < 0 || a.canvas_h < 0 || a.canvas_w < 0 ||
+      !(a.rot_deg >= 0.f))
+    return -4;
+  std::vector<int64_t> idx(indices, indices + B);
+  return static_cast<Pool*>(pool)->submit(B, [=](int b) -> int {
+    const IndexEntry& e = s->index[idx[b]];
+    const int H = static_cast<int>(e.h), W = static_cast<int>(e.w);
+    std::memcpy(out + b * stride, s->data + e.offset, size_t(H) * W * 3);
+    Rng rng(mix_key(seed, epoch, static_cast<uint64_t>(idx[b])));
+    int box[4] = {0, 0, H, W};
+    int Sh = a.canvas_h > 0 ? a.canvas_h : out_h, Sw = a.canvas_w > 0 ? a.canvas_w : out_w;
+    int rc = 0;
+    if (a.mode == 0) rrc_box(rng, H, W, a, box);
+    if (a.mode == 1) center_box(H, W, a, box);
+    // CenterCrop's offset, int(round((S - out) / 2.0)): nearbyint rounds halves to even as Python does
+    double dy = std::nearbyint((Sh - out_h) / 2.0), dx = std::nearbyint((Sw - out_w) / 2.0);
+    if (a.mode == 3) {
+      Sh = H, Sw = W;
+      const int ri = H + 2 * a.pad - out_h, rj = W + 2 * a.pad - out_w;
+      if (ri < 0 || rj < 0) rc = 4;  // RandomCrop of an image smaller than the output, padding included
+      dy = static_cast<double>(rng.randint(0, std::max(ri, 0) + 1) - a.pad);
+      dx = static_cast<double>(rng.randint(0, std::max(rj, 0) + 1) - a.pad);
+    }
+    // rounded to the float that xf records, so the matrix can be recomputed from meta and xf[6]
+    const float theta = a.rot_deg > 0.f ? static_cast<float>((2.0 * rng.uniform() - 1.0) * a.rot_deg) : 0.f;
+    const int flip = a.mode != 1 ? rng.uniform() < a.flip_p : 0;
+    int64_t* m = meta + b * 8;
+    m[0] = static_cast<int64_t>(b * stride);
+    m[1] = H, m[2] = W, m[3] = box[0], m[4] = box[1], m[5] = box[2], m[6] = box[3], m[7] = flip;
+    float* t = xf + b * 8;
+    affine_matrix(box[2], box[3], Sh, Sw, out_w, dx, dy, theta, flip, t);
+    t[6] = theta, t[7] = 0.f;
+    labels[b] = e.label;
+    return rc;
   });
 }
 

@@ -313,6 +313,10 @@ void launch_to_nhwc_s2d(const void* src, int is_u8, int nchw, int N, int C, int 
                         const float* mean, const float* stdv, bf16* dst, hipStream_t s, int block = 2);
 // shard-loader augmentation: meta [B][8] = {byte offset, H, W, y0, x0, h, w, flip} -> out [B][Ho][Wo][3]
 void launch_crop_resize(const uint8_t* src, const int64_t* meta, int B, int Ho, int Wo, uint8_t* out, hipStream_t s);
+// the same with a per-image inverse affine map xf [B][8] = {m00, m01, m02, m10, m11, m12, angle_deg, 0}
+// (output pixel -> box-relative source position) and fill 0 outside the box
+void launch_warp_crop(const uint8_t* src, const int64_t* meta, const float* xf, int B, int Ho, int Wo, uint8_t* out,
+                      hipStream_t s);
 void launch_act_bwd(const bf16* dy, const bf16* y, bf16* dx, size_t numel, int act, hipStream_t s);
 void launch_prefix_mask(const bf16* x, bf16* y, int B, int D, const int* keep, hipStream_t s);
 // Philox dropout (misc.hip): y = x * keep / (1 - p); keep from (seed, *offset_ptr, element index);

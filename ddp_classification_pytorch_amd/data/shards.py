@@ -15,7 +15,10 @@ ResNet-50 at (SURVEY.md §7.5 risk 8), so this path splits the work MI355X-first
    RandomResizedCrop algorithm from a counter RNG keyed by (seed, epoch, index);
 3. **per batch, device**: one H2D copy of the raw records, then ``dcp::crop_resize`` (bilinear
    crop+resize+flip, csrc/augment.hip) and ``dcp::to_nhwc`` / ``to_nhwc_s2d`` (normalise to bf16
-   NHWC) on a side stream; the compute stream waits on an event only.
+   NHWC) on a side stream; the compute stream waits on an event only.  Presets that rotate, pad
+   or stretch (CDR, CIFAR, PLC) take the affine route instead: the host also composes each
+   image's resize-to-canvas, rotation, flip and crop offset into one inverse-affine matrix
+   (``dcpl_submit_affine``) and ``dcp::warp_crop`` resamples the box through it, zero outside.
 
 Shard file (little-endian)::
 
@@ -26,8 +29,17 @@ Shard file (little-endian)::
 
 Differences from the PIL pipeline (documented, not hidden): the resample is plain bilinear on
 the stored (short_side-resized) image, without PIL's antialiasing filter on downscales, and
-Resize+CenterCrop is one resample of the centre box instead of two.  Presets that need
-rotation or padding (CDR, CIFAR, PLC) stay on the PIL path.
+Resize+CenterCrop is one resample of the centre box instead of two.  On the affine route:
+
+* CDR's RandomResizedCrop(256) -> RandomRotation(15) -> flip -> CenterCrop(224) is ONE bilinear
+  pass from the stored image to the 224 output, where PIL resamples bilinearly to 256 and then
+  rotates with nearest-neighbour lookups; the geometry (box, angle about the canvas centre,
+  flip, crop offset, zero fill outside the rotated canvas) is the same;
+* PLC's Resize((256, 256), BICUBIC) becomes a bilinear stretch;
+* CIFAR's RandomCrop(32, padding=4) -> flip is reproduced exactly (integer offsets, no resample).
+
+``DCP_SHARD_AFFINE=0`` puts CDR, CIFAR and PLC back on the PIL DataLoader workers over the same
+shard (for A/B runs); measurements in profiles/r11/loader_affine.txt.
 """
 from __future__ import annotations
 
@@ -157,10 +169,20 @@ class ShardDataset(torch.utils.data.Dataset):
 class AugSpec(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int32), ("resize", ctypes.c_int32), ("crop", ctypes.c_int32),
                 ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float),
-                ("ratio_lo", ctypes.c_float), ("ratio_hi", ctypes.c_float), ("flip_p", ctypes.c_float)]
+                ("ratio_lo", ctypes.c_float), ("ratio_hi", ctypes.c_float), ("flip_p", ctypes.c_float),
+                # read by dcpl_submit_affine only; zero (the 8-field form) = no rotation, no padding
+                ("rot_deg", ctypes.c_float), ("pad", ctypes.c_int32),
+                ("canvas_h", ctypes.c_int32), ("canvas_w", ctypes.c_int32)]
+
+    @property
+    def affine(self) -> bool:
+        """True when the spec needs the affine route (rotation, padding or a canvas)."""
+        return bool(self.rot_deg > 0 or self.pad > 0 or self.canvas_h > 0 or self.canvas_w > 0
+                    or self.mode in (MODE_PADCROP, MODE_STRETCH))
 
 
-MODE_RRC, MODE_CENTER, MODE_WHOLE = 0, 1, 2
+# PADCROP: RandomCrop(out, padding=pad) of the image itself; STRETCH: whole image -> fixed canvas
+MODE_RRC, MODE_CENTER, MODE_WHOLE, MODE_PADCROP, MODE_STRETCH = 0, 1, 2, 3, 4
 
 
 def aug_preset(name: str, train: bool, size: int = 224):
@@ -177,7 +199,24 @@ def aug_preset(name: str, train: bool, size: int = 224):
         if train:
             return AugSpec(MODE_RRC, 0, 0, 0.08, 1.0, 3 / 4, 4 / 3, 0.5), size
         return AugSpec(MODE_CENTER, 256, size, 0, 0, 1, 1, 0.0), size
-    raise ValueError(f"preset {name!r} needs rotation/padding: use the PIL DataLoader path")
+    if name in ("cdr", "plc", "cifar", "cifar10", "cifar100") and os.environ.get("DCP_SHARD_AFFINE", "1") == "0":
+        raise ValueError(f"preset {name!r} needs rotation/padding and DCP_SHARD_AFFINE=0: PIL DataLoader path")
+    canvas = size * 8 // 7  # the references' 256 canvas for a 224 output
+    if name == "cdr":
+        # CDR/main.py:112-130: train RRC(256) -> RandomRotation(15) -> flip -> CenterCrop(224)
+        if train:
+            return AugSpec(MODE_RRC, 0, 0, 0.08, 1.0, 3 / 4, 4 / 3, 0.5, 15.0, 0, canvas, canvas), size
+        return AugSpec(MODE_CENTER, 256, size, 0, 0, 1, 1, 0.0), size
+    if name in ("cifar", "cifar10", "cifar100"):
+        # NESTED/train.py:40-45: RandomCrop(32, padding=4) + flip; val is the stored 32x32 image
+        if train:
+            return AugSpec(MODE_PADCROP, 0, 0, 1, 1, 1, 1, 0.5, 0.0, 4, 0, 0), 32
+        return AugSpec(MODE_WHOLE, 0, 0, 1, 1, 1, 1, 0.0), 32
+    if name == "plc":
+        # PLC/FolderDataset.py: Resize((256, 256)) -> flip (train) -> CenterCrop(224); the stretch is
+        # anisotropic, so validation keeps MODE_STRETCH (MODE_CENTER's box preserves the aspect ratio)
+        return AugSpec(MODE_STRETCH, 0, 0, 1, 1, 1, 1, 0.5 if train else 0.0, 0.0, 0, canvas, canvas), size
+    raise ValueError(f"unknown shard augmentation preset {name!r}")
 
 
 _LIB = {"h": None}
@@ -205,6 +244,9 @@ def native_lib():
         lib.dcpl_submit.restype = i64
         lib.dcpl_submit.argtypes = [vp, vp, vp, ctypes.c_int, vp, i64, vp, vp, ctypes.POINTER(AugSpec),
                                     ctypes.c_uint64, ctypes.c_uint64]
+        lib.dcpl_submit_affine.restype = i64
+        lib.dcpl_submit_affine.argtypes = [vp, vp, vp, ctypes.c_int, vp, i64, vp, vp, vp, ctypes.POINTER(AugSpec),
+                                           ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int]
         lib.dcpl_wait.restype = ctypes.c_int
         lib.dcpl_wait.argtypes = [vp, i64]
         _LIB["h"] = lib
@@ -228,13 +270,24 @@ class NativeGather:
         return int(self.lib.dcpl_count(self.shard))
 
     def submit(self, indices: torch.Tensor, out: torch.Tensor, meta: torch.Tensor, labels: torch.Tensor,
-               aug: AugSpec, seed: int, epoch: int) -> int:
+               aug: AugSpec, seed: int, epoch: int, xf: torch.Tensor = None, out_hw=None) -> int:
+        """With ``xf`` (float32 [B, 8]) and ``out_hw`` the affine entry point also writes each image's
+        inverse-affine matrix; without them this is the plain crop-box call, bit for bit."""
         assert indices.dtype == torch.int64 and indices.is_contiguous() and not indices.is_cuda
         B = indices.numel()
         assert meta.shape == (B, 8) and labels.shape == (B,) and out.dtype == torch.uint8
-        t = self.lib.dcpl_submit(self.pool, self.shard, indices.data_ptr(), B, out.data_ptr(), out.numel(),
-                                 meta.data_ptr(), labels.data_ptr(), ctypes.byref(aug), int(seed) & (2**64 - 1),
-                                 int(epoch))
+        if xf is None:
+            if aug.affine:
+                raise ValueError("this AugSpec rotates, pads or stretches: submit() needs xf and out_hw")
+            t = self.lib.dcpl_submit(self.pool, self.shard, indices.data_ptr(), B, out.data_ptr(), out.numel(),
+                                     meta.data_ptr(), labels.data_ptr(), ctypes.byref(aug), int(seed) & (2**64 - 1),
+                                     int(epoch))
+        else:
+            assert xf.shape == (B, 8) and xf.dtype == torch.float32 and xf.is_contiguous() and not xf.is_cuda
+            t = self.lib.dcpl_submit_affine(self.pool, self.shard, indices.data_ptr(), B, out.data_ptr(),
+                                            out.numel(), meta.data_ptr(), xf.data_ptr(), labels.data_ptr(),
+                                            ctypes.byref(aug), int(seed) & (2**64 - 1), int(epoch),
+                                            int(out_hw[0]), int(out_hw[1]))
         if t < 0:
             raise ValueError(f"dcpl_submit rejected the batch (code {t})")
         return t
@@ -288,6 +341,8 @@ class ShardLoader:
         self.slots = [dict(buf=torch.empty(self.batch_size * stride, dtype=torch.uint8, pin_memory=pin),
                            meta=torch.empty((self.batch_size, 8), dtype=torch.int64, pin_memory=pin),
                            labels=torch.empty(self.batch_size, dtype=torch.int64, pin_memory=pin),
+                           xf=(torch.empty((self.batch_size, 8), dtype=torch.float32, pin_memory=pin)
+                               if self.aug.affine else None),
                            idx=None, event=None) for _ in range(nslots)]
         self.stream = torch.cuda.Stream(device=self.device) if self.cuda else None
 
@@ -318,8 +373,9 @@ class ShardLoader:
         B = idx.numel()
         slot["idx"] = idx
         epoch = getattr(self.sampler, "epoch", self.epoch)  # the training loop drives sampler.set_epoch
+        xf = slot["xf"][:B] if slot["xf"] is not None else None
         slot["ticket"] = self.gather.submit(idx, slot["buf"], slot["meta"][:B], slot["labels"][:B], self.aug,
-                                            self.seed, epoch)
+                                            self.seed, epoch, xf, (self.out_size, self.out_size))
 
     def _convert(self, slot):
         """Join the host gather of ``slot`` and run H2D + augment + normalise (side stream)."""
@@ -331,7 +387,10 @@ class ShardLoader:
         used = min(used, slot["buf"].numel())
         src = slot["buf"][:used].to(self.device, non_blocking=True)
         labels = slot["labels"][:B].to(self.device, non_blocking=True)
-        imgs = Fn.crop_resize(src, meta, self.out_size, self.out_size)
+        if slot["xf"] is not None:
+            imgs = Fn.warp_crop(src, meta, slot["xf"][:B], self.out_size, self.out_size)
+        else:
+            imgs = Fn.crop_resize(src, meta, self.out_size, self.out_size)
         x = Fn.to_device_nhwc(imgs, self.mean, self.std, cpad=self.cpad, nchw=False, in_scale=1.0 / 255.0,
                               s2d=self.s2d)
         out = (x, labels)

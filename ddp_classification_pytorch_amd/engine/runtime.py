@@ -110,8 +110,9 @@ class WithIndex(torch.utils.data.Dataset):
 
 
 def _shard_loaders(args, rt, tr, va, tr_s, va_s, mean, std, cpad, s2d, drop_last_train):
-    """Native loaders (C++ gather + GPU crop/resize) when the transform preset maps onto them;
-    None for presets with rotation/padding (those run the PIL DataLoader over the same shard)."""
+    """Native loaders (C++ gather + GPU crop/resize, or the affine warp for the presets that rotate,
+    pad or stretch: CDR, CIFAR, PLC).  None -- the PIL DataLoader over the same shard -- only for a
+    preset aug_preset does not know, or for those three under DCP_SHARD_AFFINE=0."""
     from ..data.shards import ShardLoader, aug_preset
 
     try:

@@ -499,6 +499,41 @@ def crop_resize(src, meta, Ho, Wo):
     return out
 
 
+def warp_crop(src, meta, xf, Ho, Wo):
+    """Inverse-affine resample of the crop box with a zero border (warp_crop_kernel in
+    csrc/augment.hip), in the kernel's fp32 arithmetic: output pixel (ox, oy) reads the box at
+    (m00*ox + m01*oy + m02, m10*ox + m11*oy + m12); inside [-0.5, w-0.5) x [-0.5, h-0.5) it is
+    bilinear at the clamped position, rounded half-up, everything else (NaN included) is 0."""
+    B = meta.shape[0]
+    out = torch.zeros((B, Ho, Wo, 3), dtype=torch.uint8, device=src.device)
+    oy = torch.arange(Ho, dtype=torch.float32).view(-1, 1)
+    ox = torch.arange(Wo, dtype=torch.float32).view(1, -1)
+    xf = xf.float()
+    for b in range(B):
+        off, H, W, y0, x0, h, w, _ = (int(v) for v in meta[b].tolist())
+        img = src[off:off + H * W * 3].view(H, W, 3)[y0:y0 + h, x0:x0 + w].float()
+        m = xf[b]
+        sx = m[0] * ox + m[1] * oy + m[2]
+        sy = m[3] * ox + m[4] * oy + m[5]
+        inside = (sx >= -0.5) & (sx < w - 0.5) & (sy >= -0.5) & (sy < h - 0.5)
+        zero = torch.zeros_like(sx)
+        sx = torch.where(inside, sx, zero).clamp(0, w - 1)
+        sy = torch.where(inside, sy, zero).clamp(0, h - 1)
+        ya = sy.long().clamp_max(h - 1)
+        xa = sx.long().clamp_max(w - 1)
+        ly = (sy - ya.float()).unsqueeze(-1)
+        lx = (sx - xa.float()).unsqueeze(-1)
+        yb = (ya + 1).clamp_max(h - 1)
+        xb = (xa + 1).clamp_max(w - 1)
+        a, bb = img[ya, xa], img[ya, xb]
+        c, d = img[yb, xa], img[yb, xb]
+        top = a + (bb - a) * lx
+        bot = c + (d - c) * lx
+        v = torch.floor(top + (bot - top) * ly + 0.5).clamp(0, 255).to(torch.uint8)
+        out[b] = torch.where(inside.unsqueeze(-1), v, torch.zeros_like(v))
+    return out
+
+
 def to_nhwc_s2d(src, nchw, in_scale, mean, std, block=2):
     cq = 4 if block == 2 else 3
     x = to_nhwc(src, nchw, cq, in_scale, mean, std)

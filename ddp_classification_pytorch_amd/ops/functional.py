@@ -1841,6 +1841,14 @@ def crop_resize(src: torch.Tensor, meta: torch.Tensor, Ho: int, Wo: int) -> torc
     return K(src).crop_resize(src, meta, int(Ho), int(Wo))
 
 
+def warp_crop(src: torch.Tensor, meta: torch.Tensor, xf: torch.Tensor, Ho: int, Wo: int) -> torch.Tensor:
+    """:func:`crop_resize` through a per-image inverse affine map: host float32 ``xf`` [B, 8] =
+    {m00, m01, m02, m10, m11, m12, angle_deg, 0} sends output pixel (ox, oy) to the box-relative
+    source position (m00*ox + m01*oy + m02, m10*ox + m11*oy + m12); bilinear inside the box, 0
+    outside it (PIL's fill).  The rotate / pad / stretch presets of data/shards.py."""
+    return K(src).warp_crop(src, meta, xf, int(Ho), int(Wo))
+
+
 # ----------------------------------------------------------------------------- space-to-depth stem
 def nhwc_to_s2d(x: torch.Tensor) -> torch.Tensor:
     """[N, H, W, C>=4] NHWC image activations (channels >= 3 zero) -> [N, H/2, W/2, 16]."""

@@ -4,6 +4,9 @@ BASELINE/main.py:81-83,97-121) or a Clothing1M list dataset into the native load
 
     python tools/pack_shards.py --folder /data/food --out /data/food --short-side 256 --workers 8
     python main.py --workload baseline --data shards --folder /data/food ...
+
+CIFAR shards are packed with ``--short-side 0`` (no resize): the CIFAR preset pads and crops the
+stored 32x32 records pixel for pixel.
 """
 import argparse
 import os
