@@ -15,6 +15,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "autotune.h"
 #include "launchers.h"
 
 using at::Tensor;
@@ -111,83 +112,103 @@ dcp::TapList fwd_taps(int KH, int KW, int pad) {
   return t;
 }
 
+// taps of the stride-1 data gradient: the forward's, mirrored (dy = pad - kh, dx = pad - kw)
+dcp::TapList dgrad_taps(int KH, int KW, int pad) {
+  dcp::TapList t = fwd_taps(KH, KW, pad);
+  for (int i = 0; i < t.n; ++i) t.dy[i] = -t.dy[i], t.dx[i] = -t.dx[i];
+  return t;
+}
+
+// a per-channel fp32 vector [C]
+void check_chan_vec(const Tensor& t, int64_t C, const char* what) {
+  CHECK_DEV(t);
+  CHECK_F32(t);
+  CHECK_CONTIG(t);
+  TORCH_CHECK(t.numel() == C, what, ": per-channel vector size");
+}
+
+// BN statistics slabs [ceil(M/128),2,Co] of a tap-GEMM output with M rows (empty without stats)
+Tensor stat_slabs(bool stats, int M, int Co, const Tensor& like) {
+  return stats ? at::empty({(M + 127) / 128, 2, Co}, f32_like(like)) : at::empty({0}, f32_like(like));
+}
+
+// The forward conv of x [N,H,W,C] bf16 with w [Co,KH,KW,C] bf16: the shape checks every forward op shares,
+// the output y [N,Ho,Wo,Co] (Ho, Wo from stride and pad, or given: conv_fwd_geo) and the tap-GEMM problem
+// that writes it, plain store; the op adds its epilogue / prologue fields.
+struct FwdConv {
+  int N, H, W, C, Co, KH, KW, Ho, Wo, M;
+  Tensor y;
+  dcp::TapList taps;
+  dcp::TapGemmProblem p;  // (p.taps points at taps: not copyable)
+
+  FwdConv(const char* op, const Tensor& x, const Tensor& w, int64_t stride, int64_t pad, bool grid_given = false,
+          int64_t Ho_ = 0, int64_t Wo_ = 0) {
+    CHECK_ACT(x);
+    CHECK_ACT(w);
+    TORCH_CHECK(x.dim() == 4 && w.dim() == 4, op, " expects NHWC input and [Co,KH,KW,Ci] weight");
+    N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+    Co = w.size(0), KH = w.size(1), KW = w.size(2);
+    TORCH_CHECK(w.size(3) == C, op, ": weight Ci mismatch");
+    TORCH_CHECK(C % 8 == 0 && Co % 8 == 0, op, " needs C and Co multiples of 8");
+    if (!grid_given) {
+      TORCH_CHECK(KH * KW <= dcp::kMaxTaps && pad <= 100 && KH <= 100, op, ": unsupported conv geometry");
+      Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+      TORCH_CHECK(Ho > 0 && Wo > 0, op, ": empty conv output");
+    } else {
+      TORCH_CHECK(KH * KW <= dcp::kMaxTaps && pad >= 0 && pad < 64, op, ": unsupported conv geometry");
+      TORCH_CHECK(Ho_ > 0 && Wo_ > 0 && (Ho_ - 1) * stride - pad < H && (Wo_ - 1) * stride - pad < W, op, " grid");
+      Ho = Ho_, Wo = Wo_;
+    }
+    // GEMM rows (pixels) index as int; element offsets are 64-bit (large per-GPU batches pass 2^32
+    // elements: tests/test_large_batch_gpu.py)
+    TORCH_CHECK((int64_t)N * H * W < (1ll << 31) && (int64_t)N * Ho * Wo < (1ll << 31), op, ": too many pixels");
+    M = N * Ho * Wo;
+    y = at::empty({N, Ho, Wo, Co}, bf16_like(x));
+    taps = fwd_taps(KH, KW, pad);
+    p.src = bp(x), p.N = N, p.Hs = H, p.Ws = W, p.Cs = C;
+    p.wt = bp(w), p.Co = Co, p.T = KH * KW;
+    p.dst = bpm(y), p.Hd = p.Hy = Ho, p.Wd = p.Wy = Wo, p.ss = stride;
+    p.taps = &taps;
+    p.zero = zero_page(x.get_device());
+  }
+  FwdConv(const FwdConv&) = delete;
+  FwdConv& operator=(const FwdConv&) = delete;
+};
+
 // x [N,H,W,C] bf16, w [Co,KH,KW,C] bf16 -> y [N,Ho,Wo,Co], stats slabs [ceil(M/128),2,Co]
 std::tuple<Tensor, Tensor> conv_fwd(const Tensor& x, const Tensor& w, int64_t stride, int64_t pad, bool stats) {
-  CHECK_ACT(x);
-  CHECK_ACT(w);
-  TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "conv_fwd expects NHWC input and [Co,KH,KW,Ci] weight");
-  const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  const int Co = w.size(0), KH = w.size(1), KW = w.size(2);
-  TORCH_CHECK(w.size(3) == C, "weight Ci mismatch");
-  TORCH_CHECK(C % 8 == 0 && Co % 8 == 0, "conv_fwd needs C and Co multiples of 8");
-  TORCH_CHECK(KH * KW <= dcp::kMaxTaps && pad <= 100 && KH <= 100, "unsupported conv geometry");
-  const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-  TORCH_CHECK(Ho > 0 && Wo > 0, "empty conv output");
-  // GEMM rows (pixels) index as int; element offsets are 64-bit (large per-GPU batches pass 2^32
-  // elements: tests/test_large_batch_gpu.py)
-  TORCH_CHECK((int64_t)N * H * W < (1ll << 31) && (int64_t)N * Ho * Wo < (1ll << 31), "conv_fwd: too many pixels");
-  auto y = at::empty({N, Ho, Wo, Co}, bf16_like(x));
-  const int M = N * Ho * Wo;
-  if (stride == 1 && pad == 1 && KH == 3 && KW == 3 && dcp::conv3x3_c64_supported(H, W, C, Co)) {
+  FwdConv f("conv_fwd", x, w, stride, pad);
+  if (stride == 1 && pad == 1 && f.KH == 3 && f.KW == 3 && dcp::conv3x3_c64_supported(f.H, f.W, f.C, f.Co)) {
     // direct 64 -> 64 channel 3x3 kernel (conv3x3.hip); statistics as (n, mean, M2) partials
-    const int blocks = dcp::conv3x3_c64_blocks(N, H, W, num_cus(x.get_device()));
-    Tensor part = stats ? at::empty({blocks, 3, Co}, f32_like(x)) : at::empty({0}, f32_like(x));
-    dcp::launch_conv3x3_c64(bp(x), bp(w), bpm(y), stats ? part.data_ptr<float>() : nullptr, zero_page(x.get_device()),
-                            N, H, W, blocks, cur_stream());
-    return {y, part};
+    const int blocks = dcp::conv3x3_c64_blocks(f.N, f.H, f.W, num_cus(x.get_device()));
+    Tensor part = stats ? at::empty({blocks, 3, f.Co}, f32_like(x)) : at::empty({0}, f32_like(x));
+    dcp::launch_conv3x3_c64(bp(x), bp(w), bpm(f.y), stats ? part.data_ptr<float>() : nullptr, f.p.zero, f.N, f.H, f.W,
+                            blocks, cur_stream());
+    return {f.y, part};
   }
-  Tensor slabs;
-  if (stats)
-    slabs = at::empty({(M + 127) / 128, 2, Co}, f32_like(x));
-  else
-    slabs = at::empty({0}, f32_like(x));
-  const auto taps = fwd_taps(KH, KW, pad);
-  dcp::launch_tap_gemm(bp(x), N, H, W, C, bp(w), Co, KH * KW, bpm(y), Ho, Wo, Ho, Wo, stride, 1, 0, 0, taps,
-                       stats ? slabs.data_ptr<float>() : nullptr, nullptr, 0, zero_page(x.get_device()),
-                       cur_stream());
-  return {y, slabs};
+  Tensor slabs = stat_slabs(stats, f.M, f.Co, x);
+  f.p.stats = stats ? slabs.data_ptr<float>() : nullptr;
+  dcp::launch_tap_gemm(f.p, cur_stream());
+  return {f.y, slabs};
 }
 
 // forward conv with an eval-mode BN folded into the store: y = act(conv(x) * scale + shift [+ res])
 // (scale / shift per output channel, fp32; the BN of running statistics, AffineEpi in launchers.h)
 Tensor conv_fwd_affine(const Tensor& x, const Tensor& w, int64_t stride, int64_t pad, const Tensor& scale,
                        const Tensor& shift, int64_t act, double slope, const optional<Tensor>& res) {
-  CHECK_ACT(x);
-  CHECK_ACT(w);
-  TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "conv_fwd_affine expects NHWC input and [Co,KH,KW,Ci] weight");
-  const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  const int Co = w.size(0), KH = w.size(1), KW = w.size(2);
-  TORCH_CHECK(w.size(3) == C && C % 8 == 0 && Co % 8 == 0, "conv_fwd_affine channels");
-  TORCH_CHECK(KH * KW <= dcp::kMaxTaps && pad <= 100 && KH <= 100, "unsupported conv geometry");
+  FwdConv f("conv_fwd_affine", x, w, stride, pad);
   TORCH_CHECK(act >= 0 && act <= 2, "conv_fwd_affine: act must be none, ReLU or leaky ReLU");
-  for (const Tensor* t : {&scale, &shift}) {
-    CHECK_DEV(*t);
-    CHECK_F32(*t);
-    CHECK_CONTIG(*t);
-    TORCH_CHECK(t->numel() == Co, "conv_fwd_affine: per-channel vector size");
-  }
-  const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
-  TORCH_CHECK(Ho > 0 && Wo > 0, "empty conv output");
-  TORCH_CHECK((int64_t)N * H * W < (1ll << 31) && (int64_t)N * Ho * Wo < (1ll << 31), "conv_fwd_affine: too many pixels");
-  auto y = at::empty({N, Ho, Wo, Co}, bf16_like(x));
-  const bf16* resp = nullptr;
+  check_chan_vec(scale, f.Co, "conv_fwd_affine scale");
+  check_chan_vec(shift, f.Co, "conv_fwd_affine shift");
   if (res.has_value()) {
     CHECK_ACT(*res);
-    TORCH_CHECK(res->sizes() == y.sizes(), "conv_fwd_affine residual shape");
-    resp = bp(*res);
+    TORCH_CHECK(res->sizes() == f.y.sizes(), "conv_fwd_affine residual shape");
+    f.p.addsrc = bp(*res);
   }
-  const auto taps = fwd_taps(KH, KW, pad);
   dcp::AffineEpi aff{scale.data_ptr<float>(), shift.data_ptr<float>(), (int)act, (float)slope};
-  dcp::launch_tap_gemm(bp(x), N, H, W, C, bp(w), Co, KH * KW, bpm(y), Ho, Wo, Ho, Wo, stride, 1, 0, 0, taps, nullptr,
-                       nullptr, 0, zero_page(x.get_device()), cur_stream(), resp, nullptr, &aff);
-  return y;
-}
-
-void check_pro_vec(const Tensor& t, int C, const char* what) {
-  CHECK_DEV(t);
-  CHECK_F32(t);
-  CHECK_CONTIG(t);
-  TORCH_CHECK(t.numel() == C, what, ": per-input-channel vector size");
+  f.p.aff = &aff;
+  dcp::launch_tap_gemm(f.p, cur_stream());
+  return f.y;
 }
 
 // 1x1 stride-1 conv of relu(x * scale + shift) with that BN + ReLU applied to the A operand in
@@ -195,42 +216,59 @@ void check_pro_vec(const Tensor& t, int C, const char* what) {
 // -> (y, BN statistics slabs of y or empty), as conv_fwd
 std::tuple<Tensor, Tensor> conv_fwd_pro(const Tensor& x, const Tensor& w, const Tensor& scale, const Tensor& shift,
                                         bool stats) {
+  FwdConv f("conv_fwd_pro", x, w, 1, 0);
+  TORCH_CHECK(f.KH == 1 && f.KW == 1 && f.C % 64 == 0, "conv_fwd_pro: 1x1 NHWC conv, C % 64 == 0");
+  check_chan_vec(scale, f.C, "conv_fwd_pro scale");
+  check_chan_vec(shift, f.C, "conv_fwd_pro shift");
+  Tensor slabs = stat_slabs(stats, f.M, f.Co, x);
+  f.p.stats = stats ? slabs.data_ptr<float>() : nullptr;
+  f.p.pscale = scale.data_ptr<float>();
+  f.p.pshift = shift.data_ptr<float>();
+  dcp::launch_tap_gemm(f.p, cur_stream());
+  return {f.y, slabs};
+}
+
+// The weight gradient dw fp32 [Co,KH,KW,C] of dy [N,Ho,Wo,Co] and x [N,H,W,C] as a problem, with the checks
+// the weight-gradient ops share (taps: the caller's, alive over the launch; scale / shift: the BN prologue on
+// x), and its launch: the split-K partial buffer is sized by the plan of the very problem that is launched.
+dcp::WgradProblem wgrad_problem(const char* op, const Tensor& dy, const Tensor& x, int stride,
+                                const dcp::TapList& taps, const Tensor* scale = nullptr,
+                                const Tensor* shift = nullptr) {
+  CHECK_ACT(dy);
   CHECK_ACT(x);
-  CHECK_ACT(w);
-  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && w.size(1) == 1 && w.size(2) == 1, "conv_fwd_pro: 1x1 NHWC conv");
-  const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3), Co = w.size(0);
-  TORCH_CHECK(w.size(3) == C && C % 64 == 0 && Co % 8 == 0, "conv_fwd_pro: C % 64 == 0, Co % 8 == 0");
-  check_pro_vec(scale, C, "conv_fwd_pro scale");
-  check_pro_vec(shift, C, "conv_fwd_pro shift");
-  TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv_fwd_pro: too many pixels");
-  auto y = at::empty({N, H, W, Co}, bf16_like(x));
-  const int M = N * H * W;
-  Tensor slabs = stats ? at::empty({(M + 127) / 128, 2, Co}, f32_like(x)) : at::empty({0}, f32_like(x));
-  const auto taps = fwd_taps(1, 1, 0);
-  dcp::launch_tap_gemm(bp(x), N, H, W, C, bp(w), Co, 1, bpm(y), H, W, H, W, 1, 1, 0, 0, taps,
-                       stats ? slabs.data_ptr<float>() : nullptr, nullptr, 0, zero_page(x.get_device()), cur_stream(),
-                       nullptr, nullptr, nullptr, scale.data_ptr<float>(), shift.data_ptr<float>());
-  return {y, slabs};
+  TORCH_CHECK(dy.dim() == 4 && x.dim() == 4 && x.size(0) == dy.size(0), op, ": batch mismatch");
+  dcp::WgradProblem p;
+  p.dy = bp(dy), p.N = dy.size(0), p.Ho = dy.size(1), p.Wo = dy.size(2), p.Co = dy.size(3);
+  p.src = bp(x), p.Hs = x.size(1), p.Ws = x.size(2), p.Cs = x.size(3), p.ss = stride;
+  TORCH_CHECK(p.Cs % 8 == 0 && p.Co % 8 == 0, op, " needs channel multiples of 8");
+  TORCH_CHECK((int64_t)p.N * p.Hs * p.Ws < (1ll << 31) && (int64_t)p.N * p.Ho * p.Wo < (1ll << 31), op,
+              ": too many pixels");
+  p.taps = &taps;
+  if (scale != nullptr) {
+    check_chan_vec(*scale, p.Cs, op);
+    check_chan_vec(*shift, p.Cs, op);
+    p.pscale = scale->data_ptr<float>(), p.pshift = shift->data_ptr<float>();
+  }
+  p.zero = zero_page(dy.get_device());
+  return p;
+}
+
+void run_wgrad(const dcp::WgradProblem& p, Tensor& dw) {
+  const int ncu = num_cus(dw.get_device());
+  const int splits = dcp::wgrad_plan_splits(p, ncu);
+  auto part = at::empty({splits > 1 ? (int64_t)dcp::split_part_elems(splits, dw.numel()) : 4}, dw.options());
+  dcp::launch_wgrad(p, dw.data_ptr<float>(), part.data_ptr<float>(), ncu, cur_stream());
 }
 
 // weight gradient of conv_fwd_pro: dW = dY^T relu(x * scale + shift), the input recomputed in the
 // B-fragment registers
 Tensor conv_wgrad_pro(const Tensor& dy, const Tensor& x, const Tensor& scale, const Tensor& shift) {
-  CHECK_ACT(dy);
-  CHECK_ACT(x);
-  const int N = dy.size(0), H = dy.size(1), W = dy.size(2), Co = dy.size(3), C = x.size(3);
-  TORCH_CHECK(x.dim() == 4 && x.size(0) == N && x.size(1) == H && x.size(2) == W, "conv_wgrad_pro: 1x1 geometry");
-  TORCH_CHECK(C % 8 == 0 && Co % 8 == 0 && C <= 2048 && !(Co <= 64 && C >= 128), "conv_wgrad_pro: channel layout");
-  check_pro_vec(scale, C, "conv_wgrad_pro scale");
-  check_pro_vec(shift, C, "conv_wgrad_pro shift");
-  TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv_wgrad_pro: too many pixels");
-  auto dw = at::empty({Co, 1, 1, C}, f32_like(dy));
   const auto taps = fwd_taps(1, 1, 0);
-  const int ncu = num_cus(dy.get_device());
-  const int splits = dcp::wgrad_plan_splits(N, H, W, Co, H, W, C, 1, taps, ncu);
-  auto part = at::empty({splits > 1 ? (int64_t)(splits + (splits + 63) / 64) * dw.numel() : 4}, f32_like(dy));
-  dcp::launch_wgrad(bp(dy), N, H, W, Co, bp(x), H, W, C, 1, taps, dw.data_ptr<float>(), part.data_ptr<float>(),
-                    zero_page(dy.get_device()), ncu, cur_stream(), scale.data_ptr<float>(), shift.data_ptr<float>());
+  const auto p = wgrad_problem("conv_wgrad_pro", dy, x, 1, taps, &scale, &shift);
+  TORCH_CHECK(p.Hs == p.Ho && p.Ws == p.Wo, "conv_wgrad_pro: 1x1 geometry");
+  TORCH_CHECK(p.Cs <= 2048 && !(p.Co <= 64 && p.Cs >= 128), "conv_wgrad_pro: channel layout");
+  auto dw = at::empty({p.Co, 1, 1, p.Cs}, f32_like(dy));
+  run_wgrad(p, dw);
   return dw;
 }
 
@@ -244,8 +282,8 @@ std::tuple<Tensor, Tensor> conv3x3_fwd_pro(const Tensor& x, const Tensor& w, con
   TORCH_CHECK(w.dim() == 4 && w.size(1) == 3 && w.size(2) == 3 && w.size(3) == C, "conv3x3_fwd_pro: [Co,3,3,C]");
   TORCH_CHECK(dcp::conv3x3_c64_supported(H, W, C, Co), "conv3x3_fwd_pro: the direct 64-channel 3x3 geometry only");
   TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv3x3_fwd_pro: too many pixels");
-  check_pro_vec(scale, C, "conv3x3_fwd_pro scale");
-  check_pro_vec(shift, C, "conv3x3_fwd_pro shift");
+  check_chan_vec(scale, C, "conv3x3_fwd_pro scale");
+  check_chan_vec(shift, C, "conv3x3_fwd_pro shift");
   auto y = at::empty({N, H, W, Co}, bf16_like(x));
   const int blocks = dcp::conv3x3_c64_blocks(N, H, W, num_cus(x.get_device()));
   Tensor part = stats ? at::empty({blocks, 3, Co}, f32_like(x)) : at::empty({0}, f32_like(x));
@@ -257,21 +295,13 @@ std::tuple<Tensor, Tensor> conv3x3_fwd_pro(const Tensor& x, const Tensor& w, con
 // weight gradient of conv3x3_fwd_pro: the direct 3x3 weight gradient recomputing relu(x * scale +
 // shift) on its staged windows
 Tensor conv3x3_wgrad_pro(const Tensor& dy, const Tensor& x, const Tensor& scale, const Tensor& shift) {
-  CHECK_ACT(dy);
-  CHECK_ACT(x);
-  const int N = dy.size(0), H = dy.size(1), W = dy.size(2), Co = dy.size(3), C = x.size(3);
-  TORCH_CHECK(x.dim() == 4 && x.size(0) == N && x.size(1) == H && x.size(2) == W, "conv3x3_wgrad_pro: geometry");
-  check_pro_vec(scale, C, "conv3x3_wgrad_pro scale");
-  check_pro_vec(shift, C, "conv3x3_wgrad_pro shift");
-  TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv3x3_wgrad_pro: too many pixels");
-  const int ncu = num_cus(dy.get_device());
-  const int s3 = dcp::wgrad3x3_splits(N, H, W, C, Co, ncu);
-  TORCH_CHECK(s3 > 0, "conv3x3_wgrad_pro: the direct 3x3 weight-gradient geometry only");
-  auto dw = at::empty({Co, 3, 3, C}, f32_like(dy));
   const auto taps = fwd_taps(3, 3, 1);
-  auto part = at::empty({(int64_t)(s3 + (s3 + 63) / 64) * dw.numel()}, f32_like(dy));
-  dcp::launch_wgrad(bp(dy), N, H, W, Co, bp(x), H, W, C, 1, taps, dw.data_ptr<float>(), part.data_ptr<float>(),
-                    zero_page(dy.get_device()), ncu, cur_stream(), scale.data_ptr<float>(), shift.data_ptr<float>());
+  const auto p = wgrad_problem("conv3x3_wgrad_pro", dy, x, 1, taps, &scale, &shift);
+  TORCH_CHECK(p.Hs == p.Ho && p.Ws == p.Wo, "conv3x3_wgrad_pro: geometry");
+  TORCH_CHECK(dcp::wgrad3x3_splits(p.N, p.Ho, p.Wo, p.Cs, p.Co, num_cus(dy.get_device())) > 0,
+              "conv3x3_wgrad_pro: the direct 3x3 weight-gradient geometry only");
+  auto dw = at::empty({p.Co, 3, 3, p.Cs}, f32_like(dy));
+  run_wgrad(p, dw);  // (the plan is the direct kernel's: checked above)
   return dw;
 }
 
@@ -300,8 +330,6 @@ std::tuple<Tensor, Tensor> act_scale_bwd(const Tensor& dy, const Tensor& y, cons
   return {dc, g};
 }
 
-// Philox dropout: (y, used) -- `offset` int64[1] device call counter (bumped here after the launch,
-// graph-capturable), `used` int64[1] receives the counter value the mask was drawn with
 // InplaceABN effective weight and its reciprocal: (|g| + eps, 1 / (|g| + eps))
 std::tuple<Tensor, Tensor> iabn_gamma(const Tensor& g, double eps) {
   CHECK_DEV(g);
@@ -324,6 +352,8 @@ Tensor sign_mul(const Tensor& d, const Tensor& g) {
   return out;
 }
 
+// Philox dropout: (y, used) -- `offset` int64[1] device call counter (bumped here after the launch,
+// graph-capturable), `used` int64[1] receives the counter value the mask was drawn with
 std::tuple<Tensor, Tensor> dropout_fwd(const Tensor& x, double p, int64_t seed, const Tensor& offset) {
   CHECK_DEV(x);
   CHECK_CONTIG(x);
@@ -372,21 +402,11 @@ Tensor adaptive_avg_pool_bwd(const Tensor& dy, int64_t H, int64_t W) {
 // oy*stride + kh - pad, columns ox*stride + kw - pad; out-of-range taps read zeros)
 std::tuple<Tensor, Tensor> conv_fwd_geo(const Tensor& x, const Tensor& w, int64_t stride, int64_t pad, int64_t Ho,
                                         int64_t Wo, bool stats) {
-  CHECK_ACT(x);
-  CHECK_ACT(w);
-  TORCH_CHECK(x.dim() == 4 && w.dim() == 4 && w.size(3) == x.size(3), "conv_fwd_geo shapes");
-  const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
-  const int Co = w.size(0), KH = w.size(1), KW = w.size(2);
-  TORCH_CHECK(C % 8 == 0 && Co % 8 == 0 && KH * KW <= dcp::kMaxTaps && pad >= 0 && pad < 64, "conv_fwd_geo geometry");
-  TORCH_CHECK(Ho > 0 && Wo > 0 && (Ho - 1) * stride - pad < H && (Wo - 1) * stride - pad < W, "conv_fwd_geo grid");
-  auto y = at::empty({N, Ho, Wo, Co}, bf16_like(x));
-  const int M = N * Ho * Wo;
-  Tensor slabs = stats ? at::empty({(M + 127) / 128, 2, Co}, f32_like(x)) : at::empty({0}, f32_like(x));
-  const auto taps = fwd_taps(KH, KW, pad);
-  dcp::launch_tap_gemm(bp(x), N, H, W, C, bp(w), Co, KH * KW, bpm(y), Ho, Wo, Ho, Wo, stride, 1, 0, 0, taps,
-                       stats ? slabs.data_ptr<float>() : nullptr, nullptr, 0, zero_page(x.get_device()),
-                       cur_stream());
-  return {y, slabs};
+  FwdConv f("conv_fwd_geo", x, w, stride, pad, true, Ho, Wo);
+  Tensor slabs = stat_slabs(stats, f.M, f.Co, x);
+  f.p.stats = stats ? slabs.data_ptr<float>() : nullptr;
+  dcp::launch_tap_gemm(f.p, cur_stream());
+  return {f.y, slabs};
 }
 
 // the space-to-depth ResNet stem: x [N,H,W,16], w [64,4,4,16] -> y [N,H,W,64] (4x4 / stride 1,
@@ -432,7 +452,7 @@ std::tuple<Tensor, Tensor> stem_bn_pool_bwd(const Tensor& dy, const Tensor& idx,
               "stem_bn_pool_bwd: tensor too large");
   const int nb = dcp::stem_bwd_blocks(N, H, num_cus(z.get_device()));
   const int pf = dcp::stem_bwd_part_floats();
-  auto part = at::empty({(int64_t)(nb + (nb + 63) / 64) * pf}, f32_like(z));
+  auto part = at::empty({(int64_t)dcp::split_part_elems(nb, pf)}, f32_like(z));
   auto tot = at::empty({pf}, f32_like(z));
   auto sums = at::empty({2, 64}, f32_like(z));
   dcp::launch_stem_bwd(bp(z), bp(x16), bp(dy), idx.data_ptr<uint8_t>(), scale.data_ptr<float>(),
@@ -451,20 +471,33 @@ Tensor stem_bwd_dw(const Tensor& tot, const Tensor& sums, const Tensor& scale, c
   return dw;
 }
 
+// The data gradient dx [N,H,W,C] of dy [N,Ho,Wo,Co] with the transposed weight wt [C,KH,KW,Co]: the checks
+// the dgrad ops share and the stride-1 tap-GEMM problem over the whole of dx (dst, taps and epilogue unset)
+dcp::TapGemmProblem dgrad_problem(const char* op, const Tensor& dy, const Tensor& wt, int64_t H, int64_t W) {
+  CHECK_ACT(dy);
+  CHECK_ACT(wt);
+  dcp::TapGemmProblem p;
+  p.src = bp(dy), p.N = dy.size(0), p.Hs = dy.size(1), p.Ws = dy.size(2), p.Cs = dy.size(3);
+  p.wt = bp(wt), p.Co = wt.size(0), p.T = wt.size(1) * wt.size(2);
+  TORCH_CHECK(wt.size(3) == p.Cs, "transposed weight Co mismatch");
+  TORCH_CHECK(p.T <= dcp::kMaxTaps, "kernel too large");
+  TORCH_CHECK(p.Co % 8 == 0 && p.Cs % 8 == 0, op, " needs channel multiples of 8");
+  TORCH_CHECK(H > 0 && W > 0, op, ": geometry");
+  TORCH_CHECK((int64_t)p.N * H * W < (1ll << 31) && (int64_t)p.N * p.Hs * p.Ws < (1ll << 31), op, ": too many pixels");
+  p.Hd = p.Hy = H, p.Wd = p.Wy = W;
+  p.zero = zero_page(dy.get_device());
+  return p;
+}
+
 // dy [N,Ho,Wo,Co], wt [C,KH,KW,Co] (transposed weight) -> dx [N,H,W,C]
 Tensor conv_dgrad(const Tensor& dy, const Tensor& wt, int64_t H, int64_t W, int64_t stride, int64_t pad,
                   const optional<Tensor>& add) {
-  CHECK_ACT(dy);
-  CHECK_ACT(wt);
-  const int N = dy.size(0), Ho = dy.size(1), Wo = dy.size(2), Co = dy.size(3);
-  const int C = wt.size(0), KH = wt.size(1), KW = wt.size(2);
-  TORCH_CHECK(wt.size(3) == Co, "transposed weight Co mismatch");
-  TORCH_CHECK(C % 8 == 0 && Co % 8 == 0, "conv_dgrad needs channel multiples of 8");
+  auto p = dgrad_problem("conv_dgrad", dy, wt, H, W);
+  const int N = p.N, Ho = p.Hs, Wo = p.Ws, Co = p.Cs, C = p.Co, KH = wt.size(1), KW = wt.size(2);
   TORCH_CHECK(stride == 1 || stride == 2, "conv_dgrad supports stride 1 and 2");
   TORCH_CHECK((H + 2 * pad - KH) / stride + 1 == Ho && (W + 2 * pad - KW) / stride + 1 == Wo, "dgrad geometry");
-  TORCH_CHECK((int64_t)N * H * W < (1ll << 31) && (int64_t)N * Ho * Wo < (1ll << 31), "conv_dgrad: too many pixels");
   auto dx = at::empty({N, H, W, C}, bf16_like(dy));
-  const bf16* z = zero_page(dy.get_device());
+  p.dst = bpm(dx);
   auto st = cur_stream();
   if (stride == 1 && pad == 1 && KH == 3 && KW == 3 && !add.has_value() && dcp::conv3x3_c64_supported(H, W, Co, C)) {
     // 64 -> 64 channel 3x3: the input gradient is the direct kernel's forward conv of dY with the
@@ -472,30 +505,21 @@ Tensor conv_dgrad(const Tensor& dy, const Tensor& wt, int64_t H, int64_t W, int6
     // one staged window per strip instead of nine tap gathers; ResNet-50 layer1 conv2 dgrad); the
     // kernel reads the taps of wt in reverse order (no flipped copy)
     const int blocks = dcp::conv3x3_c64_blocks(N, H, W, num_cus(dy.get_device()));
-    dcp::launch_conv3x3_c64(bp(dy), bp(wt), bpm(dx), nullptr, z, N, H, W, blocks, st, nullptr, nullptr, 1);
+    dcp::launch_conv3x3_c64(bp(dy), bp(wt), bpm(dx), nullptr, p.zero, N, H, W, blocks, st, nullptr, nullptr, 1);
     return dx;
   }
   if (stride == 1) {
-    dcp::TapList t;
-    t.n = KH * KW;
-    for (int kh = 0; kh < KH; ++kh)
-      for (int kw = 0; kw < KW; ++kw) {
-        const int i = kh * KW + kw;
-        t.dy[i] = pad - kh;
-        t.dx[i] = pad - kw;
-        t.widx[i] = i;
-      }
-    const bf16* addp = nullptr;
+    const auto t = dgrad_taps(KH, KW, pad);
+    p.taps = &t;
     if (add.has_value()) {
       CHECK_ACT(*add);
       TORCH_CHECK(add->sizes() == dx.sizes(), "conv_dgrad add shape");
-      addp = bp(*add);
+      p.addsrc = bp(*add);
     }
-    dcp::launch_tap_gemm(bp(dy), N, Ho, Wo, Co, bp(wt), C, KH * KW, bpm(dx), H, W, H, W, 1, 1, 0, 0, t, nullptr,
-                         nullptr, 0, z, st, addp);
+    dcp::launch_tap_gemm(p, st);
     return dx;
   }
-  // stride 2: four parity classes of the input grid.  tg_parity_streams = 1: the classes run
+  // stride 2: four parity classes of the input grid.  dgrad_parity_streams = 1: the classes run
   // concurrently on four pooled streams (fork / join through events; captured as parallel graph
   // branches), so one class's short-K tail overlaps the others (A/B)
   const bool par = dcp::g_tune[dcp::kDgradParityStreams] == 1;
@@ -508,8 +532,8 @@ Tensor conv_dgrad(const Tensor& dy, const Tensor& wt, int64_t H, int64_t W, int6
   int ncls = 0;
   for (int ph = 0; ph < 2; ++ph)
     for (int pw = 0; pw < 2; ++pw) {
-      const int Hy = (H - ph + 1) / 2, Wy = (W - pw + 1) / 2;
-      if (Hy <= 0 || Wy <= 0) continue;
+      p.Hy = (H - ph + 1) / 2, p.Wy = (W - pw + 1) / 2;
+      if (p.Hy <= 0 || p.Wy <= 0) continue;
       dcp::TapList t;
       t.n = 0;
       for (int kh = 0; kh < KH; ++kh) {
@@ -528,8 +552,9 @@ Tensor conv_dgrad(const Tensor& dy, const Tensor& wt, int64_t H, int64_t W, int6
         hipStreamWaitEvent(cs, fork_ev, 0);
         side.push_back(cs);
       }
-      dcp::launch_tap_gemm(bp(dy), N, Ho, Wo, Co, bp(wt), C, KH * KW, bpm(dx), H, W, Hy, Wy, 1, 2, ph, pw, t,
-                           nullptr, nullptr, 0, z, cs);
+      p.ds = 2, p.oy = ph, p.ox = pw;
+      p.taps = &t;
+      dcp::launch_tap_gemm(p, cs);
       ++ncls;
     }
   for (size_t i = 0; i < side.size(); ++i) {  // join
@@ -550,14 +575,10 @@ std::tuple<Tensor, Tensor> conv_dgrad_bn(const Tensor& dy, const Tensor& wt, int
                                          const optional<Tensor>& y, const optional<Tensor>& res, const Tensor& scale,
                                          const Tensor& shift, const Tensor& mean, const Tensor& invstd, int64_t act,
                                          const optional<Tensor>& mask, double slope) {
-  CHECK_ACT(dy);
-  CHECK_ACT(wt);
-  const int N = dy.size(0), Ho = dy.size(1), Wo = dy.size(2), Co = dy.size(3);
-  const int C = wt.size(0), KH = wt.size(1), KW = wt.size(2);
-  TORCH_CHECK(wt.size(3) == Co, "transposed weight Co mismatch");
-  TORCH_CHECK(C % 8 == 0 && Co % 8 == 0, "conv_dgrad_bn needs channel multiples of 8");
-  const int H = Ho - 2 * (int)pad + KH - 1, W = Wo - 2 * (int)pad + KW - 1;  // stride 1
-  TORCH_CHECK(H > 0 && W > 0, "conv_dgrad_bn: stride-1 geometry");
+  const int KH = wt.size(1), KW = wt.size(2);
+  const int H = dy.size(1) - 2 * (int)pad + KH - 1, W = dy.size(2) - 2 * (int)pad + KW - 1;  // stride 1
+  auto p = dgrad_problem("conv_dgrad_bn", dy, wt, H, W);
+  const int N = p.N, C = p.Co;
   if (y.has_value()) {
     CHECK_ACT(*y);
     TORCH_CHECK(y->dim() == 4 && y->size(0) == N && y->size(3) == C, "conv_dgrad_bn: BN input shape");
@@ -565,17 +586,11 @@ std::tuple<Tensor, Tensor> conv_dgrad_bn(const Tensor& dy, const Tensor& wt, int
   } else {
     TORCH_CHECK(mask.has_value() && act == 1, "conv_dgrad_bn: no BN input needs ReLU mask bits");
   }
-  TORCH_CHECK((int64_t)N * H * W < (1ll << 31), "conv_dgrad_bn: too many pixels");
   TORCH_CHECK(act == 0 || act == 1 || act == 2, "conv_dgrad_bn: act must be none, ReLU or leaky ReLU");
   TORCH_CHECK(act != 2 || (!mask.has_value() && !res.has_value()), "conv_dgrad_bn: leaky path has no mask / residual");
-  for (const Tensor* t : {&scale, &shift, &mean, &invstd}) {
-    CHECK_DEV(*t);
-    CHECK_F32(*t);
-    CHECK_CONTIG(*t);
-    TORCH_CHECK(t->numel() == C, "conv_dgrad_bn: per-channel vector size");
-  }
+  for (const Tensor* t : {&scale, &shift, &mean, &invstd}) check_chan_vec(*t, C, "conv_dgrad_bn");
   auto dx = at::empty({N, H, W, C}, bf16_like(dy));
-  const bf16* addp = nullptr;
+  p.dst = bpm(dx);
   int add_s2 = 0, add_hc = 0, add_wc = 0;
   if (add.has_value()) {
     CHECK_ACT(*add);
@@ -588,7 +603,7 @@ std::tuple<Tensor, Tensor> conv_dgrad_bn(const Tensor& dy, const Tensor& wt, int
                   "conv_dgrad_bn add shape: [N,H,W,C] or the stride-2 subgrid [N,ceil(H/2),ceil(W/2),C]");
       add_s2 = 1;
     }
-    addp = bp(*add);
+    p.addsrc = bp(*add);
   }
   const bf16* resp = nullptr;
   if (res.has_value()) {
@@ -607,24 +622,16 @@ std::tuple<Tensor, Tensor> conv_dgrad_bn(const Tensor& dy, const Tensor& wt, int
   const int M = N * H * W;
   const int ntm = (M + 127) / 128;
   // per-tile partials + room for the chunk sums of the two-level deterministic reduce
-  auto part = at::empty({(int64_t)(ntm + (ntm + 63) / 64) * 2 * C}, f32_like(dy));
+  auto part = at::empty({(int64_t)dcp::split_part_elems(ntm, 2 * C)}, f32_like(dy));
   auto sums = at::empty({2, C}, f32_like(dy));
-  dcp::TapList t;
-  t.n = KH * KW;
-  TORCH_CHECK(t.n <= dcp::kMaxTaps, "kernel too large");
-  for (int kh = 0; kh < KH; ++kh)
-    for (int kw = 0; kw < KW; ++kw) {
-      const int i = kh * KW + kw;
-      t.dy[i] = pad - kh;
-      t.dx[i] = pad - kw;
-      t.widx[i] = i;
-    }
+  const auto t = dgrad_taps(KH, KW, pad);
+  p.taps = &t;
   dcp::BnBwdEpi e{y.has_value() ? bp(*y) : nullptr, resp, scale.data_ptr<float>(), shift.data_ptr<float>(), mean.data_ptr<float>(),
                   invstd.data_ptr<float>(), part.data_ptr<float>(), (int)act, maskp, (float)slope, add_s2, add_hc,
                   add_wc};
+  p.bnb = &e;
   auto st = cur_stream();
-  dcp::launch_tap_gemm(bp(dy), N, Ho, Wo, Co, bp(wt), C, KH * KW, bpm(dx), H, W, H, W, 1, 1, 0, 0, t, nullptr, nullptr,
-                       0, zero_page(dy.get_device()), st, addp, &e);
+  dcp::launch_tap_gemm(p, st);
   dcp::launch_split_reduce(part.data_ptr<float>(), ntm, 2 * C, sums.data_ptr<float>(), st);
   return {dx, sums};
 }
@@ -643,105 +650,41 @@ struct WgCfg {
 const WgCfg kWgCfgs[] = {{0, 0, 0, 0, 0}, {1, 0, 0, 0, 0}, {2, 0, 0, 0, 0},  {4, 0, 0, 0, 0},
                          {8, 0, 0, 0, 0}, {0, 2, 0, 0, 0}, {0, 0, 32, 0, 0}, {0, 0, 0, 1, 0},
                          {0, 0, 0, 0, 64}, {0, 2, 0, 0, 64}, {0, 0, 0, 1, 64}};
-std::mutex g_wg_mu;
-std::unordered_map<std::string, int> g_wg_choice;
-struct WgOverride {
-  int saved[5];
-  explicit WgOverride(const WgCfg& c) {
-    saved[0] = dcp::g_tune[dcp::kWgSplitsPerCu]; saved[1] = dcp::g_tune[dcp::kWgTileMode]; saved[2] = dcp::g_tune[dcp::kWgRows]; saved[3] = dcp::g_tune[dcp::kWg3x3];
-    saved[4] = dcp::g_tune[dcp::kWgSplitCap];
-    dcp::g_tune[dcp::kWgSplitsPerCu] = c.t5; dcp::g_tune[dcp::kWgTileMode] = c.t7; dcp::g_tune[dcp::kWgRows] = c.t12; dcp::g_tune[dcp::kWg3x3] = c.t15;
-    dcp::g_tune[dcp::kWgSplitCap] = c.t27;
-  }
-  ~WgOverride() {
-    dcp::g_tune[dcp::kWgSplitsPerCu] = saved[0]; dcp::g_tune[dcp::kWgTileMode] = saved[1]; dcp::g_tune[dcp::kWgRows] = saved[2]; dcp::g_tune[dcp::kWg3x3] = saved[3];
-    dcp::g_tune[dcp::kWgSplitCap] = saved[4];
-  }
-};
+dcp::Autotuner g_wg_tuner("wgrad", "wg", (int)(sizeof(kWgCfgs) / sizeof(kWgCfgs[0])));
 }  // namespace
 
-int64_t wgrad_autotune_entries() {
-  std::lock_guard<std::mutex> lk(g_wg_mu);
-  return (int64_t)g_wg_choice.size();
+// the problem as the tuner's key: "N Ho Wo Co H W C KH KW stride pad"
+std::string wgrad_key(const dcp::WgradProblem& p, int64_t KH, int64_t KW, int64_t stride, int64_t pad) {
+  std::string key;
+  for (int64_t v : {(int64_t)p.N, (int64_t)p.Ho, (int64_t)p.Wo, (int64_t)p.Co, (int64_t)p.Hs, (int64_t)p.Ws,
+                    (int64_t)p.Cs, KH, KW, stride, pad})
+    key += (key.empty() ? "" : " ") + std::to_string(v);
+  return key;
 }
 
 // dy [N,Ho,Wo,Co], x [N,H,W,C] -> dw fp32 [Co,KH,KW,C]
 Tensor conv_wgrad(const Tensor& dy, const Tensor& x, int64_t KH, int64_t KW, int64_t stride, int64_t pad) {
-  CHECK_ACT(dy);
-  CHECK_ACT(x);
-  const int N = dy.size(0), Ho = dy.size(1), Wo = dy.size(2), Co = dy.size(3);
-  const int H = x.size(1), W = x.size(2), C = x.size(3);
-  TORCH_CHECK(x.size(0) == N, "batch mismatch");
-  TORCH_CHECK(C % 8 == 0 && Co % 8 == 0, "conv_wgrad needs channel multiples of 8");
-  TORCH_CHECK((H + 2 * pad - KH) / stride + 1 == Ho && (W + 2 * pad - KW) / stride + 1 == Wo, "wgrad geometry");
-  TORCH_CHECK((int64_t)N * H * W < (1ll << 31) && (int64_t)N * Ho * Wo < (1ll << 31), "conv_wgrad: too many pixels");
-  auto dw = at::empty({Co, KH, KW, C}, f32_like(dy));
   const auto taps = fwd_taps(KH, KW, pad);
-  const int ncu = num_cus(dy.get_device());
-  auto st = cur_stream();
-  auto run = [&]() {
-    const int splits = dcp::wgrad_plan_splits(N, Ho, Wo, Co, H, W, C, stride, taps, ncu);
-    auto part = at::empty({splits > 1 ? (int64_t)(splits + (splits + 63) / 64) * dw.numel() : 4}, f32_like(dy));
-    dcp::launch_wgrad(bp(dy), N, Ho, Wo, Co, bp(x), H, W, C, stride, taps, dw.data_ptr<float>(),
-                      part.data_ptr<float>(), zero_page(dy.get_device()), ncu, st);
-  };
-  if (dcp::g_tune[dcp::kAutotune] != 1 || dcp::g_tune[dcp::kWgSplitsPerCu] || dcp::g_tune[dcp::kWgTileMode] || dcp::g_tune[dcp::kWgRows] || dcp::g_tune[dcp::kWg3x3] ||
-      dcp::g_tune[dcp::kWgSplitCap] || (int64_t)N * Ho * Wo == 0) {
-    run();
+  const auto p = wgrad_problem("conv_wgrad", dy, x, stride, taps);
+  const int N = p.N, Ho = p.Ho, Wo = p.Wo, Co = p.Co, H = p.Hs, W = p.Ws, C = p.Cs;
+  TORCH_CHECK((H + 2 * pad - KH) / stride + 1 == Ho && (W + 2 * pad - KW) / stride + 1 == Wo, "wgrad geometry");
+  auto dw = at::empty({Co, KH, KW, C}, f32_like(dy));
+  if (dcp::g_tune[dcp::kAutotune] != 1 || dcp::g_tune[dcp::kWgSplitsPerCu] || dcp::g_tune[dcp::kWgTileMode] ||
+      dcp::g_tune[dcp::kWgRows] || dcp::g_tune[dcp::kWg3x3] || dcp::g_tune[dcp::kWgSplitCap] ||
+      (int64_t)N * Ho * Wo == 0) {
+    run_wgrad(p, dw);
     return dw;
   }
-  const std::string key = std::to_string(N) + " " + std::to_string(Ho) + " " + std::to_string(Wo) + " " +
-                          std::to_string(Co) + " " + std::to_string(H) + " " + std::to_string(W) + " " +
-                          std::to_string(C) + " " + std::to_string(KH) + " " + std::to_string(KW) + " " +
-                          std::to_string(stride) + " " + std::to_string(pad);
-  int choice = -1;
-  {
-    std::lock_guard<std::mutex> lk(g_wg_mu);
-    auto it = g_wg_choice.find(key);
-    if (it != g_wg_choice.end()) choice = it->second;
-  }
-  if (choice < 0) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-      run();
-      return dw;
-    }
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    float best = 1e30f, t_heur = 1e30f;
-    choice = 0;
-    for (int c = 0; c < (int)(sizeof(kWgCfgs) / sizeof(kWgCfgs[0])); ++c) {
-      WgOverride ov(kWgCfgs[c]);
-      run();  // warm
-      float t = 1e30f;
-      for (int r = 0; r < 3; ++r) {
-        hipEventRecord(e0, st);
-        run();
-        hipEventRecord(e1, st);
-        hipEventSynchronize(e1);
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, e0, e1);
-        t = std::min(t, ms);
-      }
-      if (c == 0) {
-        t_heur = best = t;
-      } else if (t < best && t < 0.98f * t_heur) {  // must beat the heuristic by 2 % to replace it
-        best = t;
-        choice = c;
-      }
-    }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    {
-      std::lock_guard<std::mutex> lk(g_wg_mu);
-      g_wg_choice[key] = choice;
-    }
-    if (getenv("DCP_AUTOTUNE_LOG"))
-      fprintf(stderr, "[dcp-autotune] wgrad %s -> cfg %d (%.1f us)\n", key.c_str(), choice, best * 1e3f);
-  }
-  WgOverride ov(kWgCfgs[choice]);
-  run();
+  auto run_with = [&](int c) {
+    const WgCfg& cfg = kWgCfgs[c];
+    dcp::TuneGuard ov({dcp::kWgSplitsPerCu, dcp::kWgTileMode, dcp::kWgRows, dcp::kWg3x3, dcp::kWgSplitCap},
+                      {cfg.t5, cfg.t7, cfg.t12, cfg.t15, cfg.t27});
+    run_wgrad(p, dw);  // (plans under the candidate's slots: the split count is part of it)
+  };
+  const int choice =
+      g_wg_tuner.pick(wgrad_key(p, KH, KW, stride, pad), cur_stream(), [](int) { return false; }, run_with);
+  if (choice < 0) run_wgrad(p, dw);  // a new problem inside a capture: the heuristic
+  else run_with(choice);
   return dw;
 }
 
@@ -771,13 +714,16 @@ Tensor conv1x1_cat(const Tensor& x, const optional<Tensor>& x2, const Tensor& w,
     bptr = bias->data_ptr<float>();
   }
   auto out = at::empty({N, H, W, Co}, bf16_like(x));
-  dcp::TapList t;
-  t.n = 1;
-  t.dy[0] = t.dx[0] = t.widx[0] = 0;
+  const auto t = fwd_taps(1, 1, 0);
   // (one source: the [Co][C] weight as a one-tap matrix; two: launch_tap_gemm's ldw = C + C2)
-  dcp::launch_tap_gemm(bp(x), N, H, W, C, bp(w), Co, 1, bpm(out), H, W, H, W, 1, 1, 0, 0, t, nullptr, nullptr, 0,
-                       zero_page(x.get_device()), cur_stream(), nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                       x2.has_value() ? bp(*x2) : nullptr, C2, bptr);
+  dcp::TapGemmProblem p;
+  p.src = bp(x), p.N = N, p.Hs = H, p.Ws = W, p.Cs = C;
+  p.wt = bp(w), p.Co = Co, p.T = 1;
+  p.dst = bpm(out), p.Hd = p.Hy = H, p.Wd = p.Wy = W;
+  p.taps = &t;
+  p.src2 = x2.has_value() ? bp(*x2) : nullptr, p.Cs2 = C2, p.bias2 = bptr;
+  p.zero = zero_page(x.get_device());
+  dcp::launch_tap_gemm(p, cur_stream());
   return out;
 }
 
@@ -800,12 +746,7 @@ std::tuple<Tensor, Tensor> conv1x1_bn_lin_bwd(const Tensor& g, const Tensor& a2,
   TORCH_CHECK(dcp::bn_lin_supported(m, C), "conv1x1_bn_lin_bwd: channels must be multiples of 64");
   TORCH_CHECK(w3.numel() == (int64_t)C * m && w3.size(0) == C && wt.numel() == (int64_t)C * m && wt.size(0) == m,
               "conv1x1_bn_lin_bwd: weight shapes");
-  for (const Tensor* t : {&scale, &invstd}) {
-    CHECK_DEV(*t);
-    CHECK_CONTIG(*t);
-    CHECK_F32(*t);
-    TORCH_CHECK(t->numel() == C, "conv1x1_bn_lin_bwd: per-channel vector size");
-  }
+  for (const Tensor* t : {&scale, &invstd}) check_chan_vec(*t, C, "conv1x1_bn_lin_bwd");
   CHECK_DEV(sums);
   CHECK_CONTIG(sums);
   CHECK_F32(sums);
@@ -886,20 +827,12 @@ std::tuple<Tensor, Tensor> bn_lin_s2(const Tensor& g, const Tensor& a2, const Te
 
 // weight gradient for conv_fwd_geo's geometry (output grid taken from dy)
 Tensor conv_wgrad_geo(const Tensor& dy, const Tensor& x, int64_t KH, int64_t KW, int64_t stride, int64_t pad) {
-  CHECK_ACT(dy);
-  CHECK_ACT(x);
-  const int N = dy.size(0), Ho = dy.size(1), Wo = dy.size(2), Co = dy.size(3);
-  const int H = x.size(1), W = x.size(2), C = x.size(3);
-  TORCH_CHECK(x.size(0) == N && C % 8 == 0 && Co % 8 == 0 && KH * KW <= dcp::kMaxTaps, "conv_wgrad_geo shapes");
-  TORCH_CHECK(pad >= 0 && pad < 64 && (Ho - 1) * stride - pad < H && (Wo - 1) * stride - pad < W,
-              "conv_wgrad_geo grid");
-  auto dw = at::empty({Co, KH, KW, C}, f32_like(dy));
   const auto taps = fwd_taps(KH, KW, pad);
-  const int ncu = num_cus(dy.get_device());
-  const int splits = dcp::wgrad_plan_splits(N, Ho, Wo, Co, H, W, C, stride, taps, ncu);
-  auto part = at::empty({splits > 1 ? (int64_t)(splits + (splits + 63) / 64) * dw.numel() : 4}, f32_like(dy));
-  dcp::launch_wgrad(bp(dy), N, Ho, Wo, Co, bp(x), H, W, C, stride, taps, dw.data_ptr<float>(),
-                    part.data_ptr<float>(), zero_page(dy.get_device()), ncu, cur_stream());
+  const auto p = wgrad_problem("conv_wgrad_geo", dy, x, stride, taps);
+  TORCH_CHECK(pad >= 0 && pad < 64 && (p.Ho - 1) * stride - pad < p.Hs && (p.Wo - 1) * stride - pad < p.Ws,
+              "conv_wgrad_geo grid");
+  auto dw = at::empty({p.Co, KH, KW, p.Cs}, f32_like(dy));
+  run_wgrad(p, dw);
   return dw;
 }
 
@@ -916,14 +849,17 @@ Tensor linear_fwd(const Tensor& x, const Tensor& w, const optional<Tensor>& bias
     TORCH_CHECK(bias->numel() >= 1 && bias->numel() <= Np, "bias longer than the output width");
   }
   auto y = at::empty({B, Np}, bf16_like(x));
-  dcp::TapList t;
-  t.n = 1;
-  t.dy[0] = t.dx[0] = t.widx[0] = 0;
+  const auto t = fwd_taps(1, 1, 0);
   TORCH_CHECK(act >= 0 && act <= 2, "linear act must be 0 (none), 1 (relu) or 2 (sigmoid)");
+  dcp::TapGemmProblem p;  // B pixels of a 1 x 1 image
+  p.src = bp(x), p.N = B, p.Hs = p.Ws = 1, p.Cs = K;
+  p.wt = bp(w), p.Co = Np, p.T = 1;
+  p.dst = bpm(y), p.Hd = p.Wd = p.Hy = p.Wy = 1;
+  p.taps = &t;
   // an unpadded bias (the output width rounded up for the GEMM): columns past it add 0
-  dcp::launch_tap_gemm(bp(x), B, 1, 1, K, bp(w), Np, 1, bpm(y), 1, 1, 1, 1, 1, 1, 0, 0, t, nullptr, fp(bias),
-                       (int)act, zero_page(x.get_device()), cur_stream(), nullptr, nullptr, nullptr, nullptr,
-                       nullptr, bias.has_value() ? (int)bias->numel() : 0);
+  p.bias = fp(bias), p.nbias = bias.has_value() ? (int)bias->numel() : 0, p.relu = (int)act;
+  p.zero = zero_page(x.get_device());
+  dcp::launch_tap_gemm(p, cur_stream());
   return y;
 }
 
@@ -934,14 +870,13 @@ Tensor linear_wgrad(const Tensor& dy, const Tensor& x) {
   const int B = dy.size(0), Np = dy.size(1), K = x.size(1);
   TORCH_CHECK(x.size(0) == B && K % 8 == 0 && Np % 8 == 0, "linear_wgrad shapes");
   auto dw = at::empty({Np, K}, f32_like(dy));
-  dcp::TapList t;
-  t.n = 1;
-  t.dy[0] = t.dx[0] = t.widx[0] = 0;
-  const int ncu = num_cus(dy.get_device());
-  const int splits = dcp::wgrad_splits(B, Np, K, 1, ncu, nullptr);
-  auto part = at::empty({splits > 1 ? (int64_t)(splits + (splits + 63) / 64) * dw.numel() : 4}, f32_like(dy));
-  dcp::launch_wgrad(bp(dy), B, 1, 1, Np, bp(x), 1, 1, K, 1, t, dw.data_ptr<float>(), part.data_ptr<float>(),
-                    zero_page(dy.get_device()), ncu, cur_stream());
+  const auto t = fwd_taps(1, 1, 0);
+  dcp::WgradProblem p;  // B pixels of a 1 x 1 image
+  p.dy = bp(dy), p.N = B, p.Ho = p.Wo = 1, p.Co = Np;
+  p.src = bp(x), p.Hs = p.Ws = 1, p.Cs = K;
+  p.taps = &t;
+  p.zero = zero_page(dy.get_device());
+  run_wgrad(p, dw);
   return dw;
 }
 
@@ -1038,7 +973,7 @@ std::tuple<Tensor, Tensor> grouped_conv_dgrad_bn(const Tensor& dy, const Tensor&
   auto dx = at::empty({N, H, W, C}, bf16_like(dy));
   auto frag = at::empty({std::max(dcp::gconv_frag_elems(C, groups, KH, KW), 8)}, bf16_like(dy));
   const int npb = dcp::gconv_fwd_stat_blocks(N * H * W);
-  auto part = at::empty({(int64_t)npb * 2 * C + ((npb + 63) / 64) * 2 * C}, f32_like(dy));
+  auto part = at::empty({(int64_t)dcp::split_part_elems(npb, 2 * C)}, f32_like(dy));
   dcp::GconvBnBwd bn{bp(z), scale.data_ptr<float>(), shift.data_ptr<float>(), mean.data_ptr<float>(),
                      invstd.data_ptr<float>(), part.data_ptr<float>()};
   if (!dcp::launch_gconv_mfma_dgrad(bp(dy), bp(w), bpm(dx), bpm(frag), N, H, W, C, Ho, Wo, Co, groups, KH, KW, stride,
@@ -1433,15 +1368,6 @@ Tensor maxpool_bwd(const Tensor& dy, const Tensor& idx, int64_t H, int64_t W, in
   return dx;
 }
 
-static void check_bn_vecs(std::initializer_list<const Tensor*> ts, int C) {
-  for (const Tensor* t : ts) {
-    CHECK_DEV(*t);
-    CHECK_F32(*t);
-    CHECK_CONTIG(*t);
-    TORCH_CHECK(t->numel() == C, "per-channel vector size");
-  }
-}
-
 static bool bn_pool_ok(int C) { return C % 8 == 0 && 256 % (C / 8) == 0; }
 
 // max pool of act(x*scale + shift) (the stem BN-apply + ReLU + pool in one pass) -> (y, argmax)
@@ -1450,7 +1376,7 @@ std::tuple<Tensor, Tensor> bn_act_maxpool(const Tensor& x, const Tensor& scale, 
   CHECK_ACT(x);
   const int N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   TORCH_CHECK(bn_pool_ok(C) && k * k <= 255 && (act == 0 || act == 1), "bn_act_maxpool shapes");
-  check_bn_vecs({&scale, &shift}, C);
+  for (const Tensor* t : {&scale, &shift}) check_chan_vec(*t, C, "maxpool_bn");
   const int Ho = (H + 2 * p - k) / s + 1, Wo = (W + 2 * p - k) / s + 1;
   auto y = at::empty({N, Ho, Wo, C}, x.options());
   auto idx = at::empty({N, Ho, Wo, C}, x.options().dtype(at::kByte));
@@ -1469,7 +1395,7 @@ Tensor maxpool_bn_bwd_reduce(const Tensor& dy, const Tensor& idx, const Tensor& 
   const int Ho = dy.size(1), Wo = dy.size(2);
   TORCH_CHECK(bn_pool_ok(C) && dy.size(0) == N && dy.size(3) == C && idx.sizes() == dy.sizes(), "maxpool_bn shapes");
   TORCH_CHECK(Ho == (H + 2 * p - k) / s + 1 && Wo == (W + 2 * p - k) / s + 1, "maxpool_bn geometry");
-  check_bn_vecs({&scale, &shift, &mean, &invstd}, C);
+  for (const Tensor* t : {&scale, &shift, &mean, &invstd}) check_chan_vec(*t, C, "maxpool_bn_bwd");
   auto part = at::empty({dcp::maxpool_bn_bwd_blocks(), 2, C}, f32_like(x));
   auto sums = at::empty({2, C}, f32_like(x));
   dcp::launch_maxpool_bn_bwd(bp(dy), idx.data_ptr<uint8_t>(), bp(x), N, H, W, C, Ho, Wo, k, s, p,
@@ -1489,7 +1415,7 @@ Tensor maxpool_bn_bwd_elemt(const Tensor& dy, const Tensor& idx, const Tensor& x
   const int Ho = dy.size(1), Wo = dy.size(2);
   TORCH_CHECK(bn_pool_ok(C) && dy.size(0) == N && dy.size(3) == C && idx.sizes() == dy.sizes(), "maxpool_bn shapes");
   TORCH_CHECK(Ho == (H + 2 * p - k) / s + 1 && Wo == (W + 2 * p - k) / s + 1, "maxpool_bn geometry");
-  check_bn_vecs({&scale, &shift, &mean, &invstd}, C);
+  for (const Tensor* t : {&scale, &shift, &mean, &invstd}) check_chan_vec(*t, C, "maxpool_bn_bwd");
   TORCH_CHECK(sums.numel() == 2 * C && sums.is_contiguous(), "sums [2, C]");
   auto dx = at::empty_like(x);
   dcp::launch_maxpool_bn_bwd(bp(dy), idx.data_ptr<uint8_t>(), bp(x), N, H, W, C, Ho, Wo, k, s, p,
@@ -2147,47 +2073,14 @@ Tensor table_fill(const Tensor& host, const Tensor& device_like) {
   return out;
 }
 
-int64_t autotune_entries() { return dcp::tap_gemm_tuned_count() + wgrad_autotune_entries(); }
+int64_t autotune_entries() { return dcp::tap_gemm_tuned_count() + g_wg_tuner.size(); }
 
 // the autotuner's decisions (tap GEMM "tg\t..." and weight-gradient "wg\t..." lines) for a tuning
 // cache file (DCP_TUNE_CACHE, _ext.py): a later process replays them without timing anything
-std::string autotune_export() {
-  std::string out;
-  const std::string tg = dcp::tap_gemm_tune_export();
-  size_t pos = 0;
-  while (pos < tg.size()) {
-    const size_t nl = tg.find('\n', pos);
-    out += "tg\t" + tg.substr(pos, (nl == std::string::npos ? tg.size() : nl) - pos) + "\n";
-    pos = nl == std::string::npos ? tg.size() : nl + 1;
-  }
-  std::lock_guard<std::mutex> lk(g_wg_mu);
-  for (const auto& kv : g_wg_choice) out += "wg\t" + kv.first + "\t" + std::to_string(kv.second) + "\n";
-  return out;
-}
+std::string autotune_export() { return dcp::tap_gemm_tune_export() + g_wg_tuner.export_text(); }
 
 int64_t autotune_import(const std::string& text) {
-  std::string tg;
-  int64_t n = 0;
-  const int nwg = (int)(sizeof(kWgCfgs) / sizeof(kWgCfgs[0]));
-  size_t pos = 0;
-  while (pos < text.size()) {
-    size_t nl = text.find('\n', pos);
-    if (nl == std::string::npos) nl = text.size();
-    const std::string line = text.substr(pos, nl - pos);
-    pos = nl + 1;
-    if (line.compare(0, 3, "tg\t") == 0) {
-      tg += line.substr(3) + "\n";
-    } else if (line.compare(0, 3, "wg\t") == 0) {
-      const size_t tab = line.rfind('\t');
-      if (tab <= 3) continue;
-      const int c = atoi(line.c_str() + tab + 1);
-      if (c < 0 || c >= nwg) continue;
-      std::lock_guard<std::mutex> lk(g_wg_mu);
-      g_wg_choice[line.substr(3, tab - 3)] = c;
-      ++n;
-    }
-  }
-  return n + dcp::tap_gemm_tune_import(tg);
+  return dcp::tap_gemm_tune_import(text) + g_wg_tuner.import_text(text);
 }
 
 void set_tuning(int64_t idx, int64_t value) {

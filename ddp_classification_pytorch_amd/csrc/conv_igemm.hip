@@ -34,11 +34,10 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <mutex>
 #include <string>
 #include <type_traits>
-#include <unordered_map>
 
+#include "autotune.h"
 #include "common.cuh"
 #include "launchers.h"
 
@@ -2216,48 +2215,61 @@ static int tg_split_slices(int M, int Co, int K) {
   return ks >= 2 ? ks : 0;
 }
 
-static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
-                          const bf16* wt, int Co, int T,
-                          bf16* dst, int Hd, int Wd, int Hy, int Wy, int ss, int ds, int oy, int ox,
-                          const TapList& taps, float* stats, const float* bias, int relu,
-                          const bf16* zero, hipStream_t stream, const bf16* addsrc, const BnBwdEpi* bnb,
-                          const AffineEpi* aff, const float* pscale, const float* pshift, int nbias,
-                          const bf16* src2, int Cs2, const float* bias2) {
+// the plain 1x1 stride-1 store GEMM dst[M][Co] = src[M][Cs] wt[Co][Cs]^T (+ statistics) on FAST shapes: what
+// the weight-stationary and the store-decoupled kernels (conv_ws.hip, conv1x1_ps.hip) compute
+static bool plain_1x1(const TapGemmProblem& q) {
+  const TapList& taps = *q.taps;
+  const bool fast = ((q.Cs / 8) & 7) == 0 && taps.n <= 32;
+  return fast && taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 && taps.widx[0] == 0 && q.ss == 1 && q.ds == 1 &&
+         q.oy == 0 && q.ox == 0 && q.Hd == q.Hy && q.Wd == q.Wy && q.Hs == q.Hy && q.Ws == q.Wy && q.T == 1 &&
+         q.addsrc == nullptr && q.aff == nullptr && q.bnb == nullptr && q.pscale == nullptr && q.bias == nullptr &&
+         q.relu == 0 && q.src2 == nullptr;  // (no bias, ReLU or BN backward: the plain / statistics epilogue)
+}
+// ... and their shape limits hold (K, Co, rows)
+static bool ws_applies(const TapGemmProblem& q) {
+  return plain_1x1(q) && conv1x1_ws_supported(q.Cs, q.Co, (long)q.N * q.Hy * q.Wy);
+}
+static bool ps_applies(const TapGemmProblem& q) {
+  return plain_1x1(q) && conv1x1_ps_supported(q.Cs, q.Co, (long)q.N * q.Hy * q.Wy);
+}
+
+static void tap_gemm_impl(const TapGemmProblem& q, hipStream_t stream) {
+  const TapList& taps = *q.taps;
   TapGemmParams p;
-  p.src2 = src2; p.bias2 = bias2; p.Cs2 = src2 ? Cs2 : 0; p.woff2 = T * Cs; p.nkt1 = 0;
-  p.pscale = pscale;
-  p.pshift = pshift;
-  p.src = src; p.wt = wt; p.dst = dst; p.stats = stats; p.zero = zero; p.addsrc = addsrc;
-  p.fscale = aff ? aff->scale : nullptr;
-  p.fshift = aff ? aff->shift : nullptr;
-  p.fact = aff ? aff->act : 0;
-  p.fslope = aff ? aff->slope : 0.f;
-  if (aff != nullptr && (stats != nullptr || bias != nullptr || relu != 0 || bnb != nullptr)) {
+  p.src2 = q.src2; p.bias2 = q.bias2; p.Cs2 = q.src2 ? q.Cs2 : 0; p.woff2 = q.T * q.Cs; p.nkt1 = 0;
+  p.pscale = q.pscale;
+  p.pshift = q.pshift;
+  p.src = q.src; p.wt = q.wt; p.dst = q.dst; p.stats = q.stats; p.zero = q.zero; p.addsrc = q.addsrc;
+  p.fscale = q.aff ? q.aff->scale : nullptr;
+  p.fshift = q.aff ? q.aff->shift : nullptr;
+  p.fact = q.aff ? q.aff->act : 0;
+  p.fslope = q.aff ? q.aff->slope : 0.f;
+  if (q.aff != nullptr && (q.stats != nullptr || q.bias != nullptr || q.relu != 0 || q.bnb != nullptr)) {
     fprintf(stderr, "launch_tap_gemm: the folded BN epilogue is a plain forward store\n");
     abort();
   }
-  p.bnb = bnb ? *bnb : BnBwdEpi{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0.f, 0, 0, 0};
-  p.Hs = Hs; p.Ws = Ws; p.Cs = Cs;
-  p.Hy = Hy; p.Wy = Wy; p.ss = ss;
-  p.Hd = Hd; p.Wd = Wd; p.ds = ds; p.oy = oy; p.ox = ox;
-  p.Co = Co; p.T = T; p.M = N * Hy * Wy;
-  p.ntaps = taps.n; p.cpt = Cs / 8; p.ldw = T * Cs + p.Cs2;
+  p.bnb = q.bnb ? *q.bnb : BnBwdEpi{};
+  p.Hs = q.Hs; p.Ws = q.Ws; p.Cs = q.Cs;
+  p.Hy = q.Hy; p.Wy = q.Wy; p.ss = q.ss;
+  p.Hd = q.Hd; p.Wd = q.Wd; p.ds = q.ds; p.oy = q.oy; p.ox = q.ox;
+  p.Co = q.Co; p.T = q.T; p.M = q.N * q.Hy * q.Wy;
+  p.ntaps = taps.n; p.cpt = q.Cs / 8; p.ldw = q.T * q.Cs + p.Cs2;
   p.nkt = (taps.n * p.cpt + 7) / 8;
-  p.relu = relu; p.bias = bias; p.nbias = (nbias > 0 && nbias < Co) ? nbias : Co;
-  p.div_wy = make_fastdiv(Wy); p.div_hy = make_fastdiv(Hy); p.div_cpt = make_fastdiv(p.cpt);
+  p.relu = q.relu; p.bias = q.bias; p.nbias = (q.nbias > 0 && q.nbias < q.Co) ? q.nbias : q.Co;
+  p.div_wy = make_fastdiv(q.Wy); p.div_hy = make_fastdiv(q.Hy); p.div_cpt = make_fastdiv(p.cpt);
   for (int i = 0; i < taps.n; ++i)
     p.tap[i] = (taps.dy[i] & 0xff) | ((taps.dx[i] & 0xff) << 8) | ((taps.widx[i] & 0xffff) << 16);
   if (p.M == 0) return;
   const int ntm = (p.M + 127) / 128;
-  int epi = (bias != nullptr || relu != 0) ? 2 : (stats != nullptr ? 1 : 0);
-  if (bnb != nullptr) {
-    if (ds != 1 || Hd != Hy || Wd != Wy || stats != nullptr || bias != nullptr || relu != 0) {
+  int epi = (q.bias != nullptr || q.relu != 0) ? 2 : (q.stats != nullptr ? 1 : 0);
+  if (q.bnb != nullptr) {
+    if (q.ds != 1 || q.Hd != q.Hy || q.Wd != q.Wy || q.stats != nullptr || q.bias != nullptr || q.relu != 0) {
       fprintf(stderr, "launch_tap_gemm: fused BN backward needs a plain stride-1 dgrad\n");
       abort();
     }
-    epi = bnb->mask != nullptr ? 4 : 3;
-    if (bnb->y == nullptr) {  // no BN input: the masked epilogue without the xhat sum (ReLU bits only)
-      if (bnb->mask == nullptr || bnb->act != 1) {
+    epi = q.bnb->mask != nullptr ? 4 : 3;
+    if (q.bnb->y == nullptr) {  // no BN input: the masked epilogue without the xhat sum (ReLU bits only)
+      if (q.bnb->mask == nullptr || q.bnb->act != 1) {
         fprintf(stderr, "launch_tap_gemm: a fused BN backward without the BN input needs ReLU mask bits\n");
         abort();
       }
@@ -2265,8 +2277,8 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
     }
   }
   const bool fast = (p.cpt & 7) == 0 && taps.n <= 32;  // FAST: 32-bit tap-validity masks
-  if (src2 != nullptr && !(fast && epi == 0 && aff == nullptr && pscale == nullptr && Cs2 > 0 && Cs2 % 64 == 0 &&
-                           Co % 8 == 0 && taps.n >= 1)) {
+  if (q.src2 != nullptr && !(fast && epi == 0 && q.aff == nullptr && q.pscale == nullptr && q.Cs2 > 0 &&
+                             q.Cs2 % 64 == 0 && q.Co % 8 == 0 && taps.n >= 1)) {
     fprintf(stderr, "launch_tap_gemm: the second source needs a plain FAST store GEMM and Cs2 %% 64 == 0\n");
     abort();
   }
@@ -2280,17 +2292,17 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   p.sk_on = g_tune[kTgBigSK] == 1 ? 1 : (g_tune[kTgBigSK] >= 3 ? g_tune[kTgBigSK] : 0);
   p.sk_ws = nullptr;
   p.sk_flags = nullptr;
-  p.ksplit = tg_split_slices(p.M, Co, taps.n * Cs);  // (the 128-row kernels; tile widths 64 / 128 / 256)
-  if (src2 != nullptr) p.ksplit = 0;  // (the split instantiations have no second source)
-  p.k64 = (taps.n * Cs + 63) / 64;
+  p.ksplit = tg_split_slices(p.M, q.Co, taps.n * q.Cs);  // (the 128-row kernels; tile widths 64 / 128 / 256)
+  if (q.src2 != nullptr) p.ksplit = 0;  // (the split instantiations have no second source)
+  p.k64 = (taps.n * q.Cs + 63) / 64;
   p.kp = nullptr;
   p.kmode = 0;
-  int bn = Co <= 64 ? 64 : 128, ns = 2;
+  int bn = q.Co <= 64 ? 64 : 128, ns = 2;
   // a short grid (< 1.5 rounds of 256 CUs at 128-channel tiles: batch 32-128 from stage 2 on, the
   // stride-2 parity classes, the linear heads) takes 64-channel tiles, twice the workgroups: the
   // per-shape autotuner (DCP_AUTOTUNE) picked them on every such ResNet-50 shape at batch 32
   // (4,616 -> 4,939 img/s), e.g. the 7x7 512-channel 3x3 convs 52 -> 104 workgroups
-  if (bn == 128 && fast && (long)ntm * ((Co + 127) / 128) < 384) bn = 64;
+  if (bn == 128 && fast && (long)ntm * ((q.Co + 127) / 128) < 384) bn = 64;
   if (env_bn > 0 && fast) bn = env_bn;
   if (env_ns > 0 && fast) ns = env_ns;
   if (!fast) ns = 2;
@@ -2304,29 +2316,28 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   bool bk32 = (fast && g_tune[kTgKDepth] == 32 && ns >= 2 && ns <= 4) || (!fast && g_tune[kNarrowKDepth] == 32);
   // (K = 64, one 64-deep k-tile, measured faster with the 64-deep tile: 487 vs 511 us on the R50
   // stage-1 expansion at b1024, tools/fwd_epi_bench.py)
-  if (fast && env_ns == 0 && g_tune[kTgKDepth] != 64 && taps.n == 1 && Cs > 64 && Cs <= 1024 && bn == 128) bk32 = true;
+  if (fast && env_ns == 0 && g_tune[kTgKDepth] != 64 && taps.n == 1 && q.Cs > 64 && q.Cs <= 1024 && bn == 128)
+    bk32 = true;
   // big-tile kernel (tap_gemm_big_kernel): FAST, plain / statistics epilogue, >= 128 output
   // channels.  g_tune[kTgBig]: 1 = on wherever it applies (256 x 256 for Co >= 256, else 256 x 128),
   // 3 = 256 x 128 only, 2 = off, 0 = heuristic (big_tile_pick)
   // weight-stationary persistent kernel (conv_ws.hip) for plain 1x1 stride-1 GEMMs with K <= 256:
   // g_tune[kTgWs] = 1 on wherever it applies (the autotuner's candidate), 2 off, 0 = heuristic (off)
-  const bool plain1x1 = fast && (epi == 0 || epi == 1) && taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 &&
-                        taps.widx[0] == 0 && ss == 1 && ds == 1 && oy == 0 && ox == 0 && Hd == Hy && Wd == Wy &&
-                        Hs == Hy && Ws == Wy && T == 1 && addsrc == nullptr && aff == nullptr && bnb == nullptr &&
-                        pscale == nullptr && bias == nullptr && relu == 0 && src2 == nullptr;
-  if (g_tune[kTgWs] == 1 && plain1x1 && conv1x1_ws_supported(Cs, Co, p.M)) {
-    if (p.ablate == 0 && launch_conv1x1_ws(src, wt, T * Cs, dst, stats, zero, p.M, Cs, Co, stream)) return;
+  if (g_tune[kTgWs] == 1 && ws_applies(q)) {
+    if (p.ablate == 0 &&
+        launch_conv1x1_ws(q.src, q.wt, q.T * q.Cs, q.dst, q.stats, q.zero, p.M, q.Cs, q.Co, stream))
+      return;
   }
   // store-decoupled loader / consumer 1x1 kernel (conv1x1_ps.hip): g_tune[kTgPs] = 1 on wherever it
   // applies with 4 consumer waves, 3 with 8 (autotuner candidates), 2 off, 0 = heuristic (off)
-  if ((g_tune[kTgPs] == 1 || g_tune[kTgPs] == 3) && plain1x1 && conv1x1_ps_supported(Cs, Co, p.M)) {
-    if (launch_conv1x1_ps(src, wt, T * Cs, dst, stats, zero, p.M, Cs, Co, p.ablate, g_tune[kTgPs] == 3 ? 8 : 4,
-                          stream))
+  if ((g_tune[kTgPs] == 1 || g_tune[kTgPs] == 3) && ps_applies(q)) {
+    if (launch_conv1x1_ps(q.src, q.wt, q.T * q.Cs, q.dst, q.stats, q.zero, p.M, q.Cs, q.Co, p.ablate,
+                          g_tune[kTgPs] == 3 ? 8 : 4, stream))
       return;
   }
-  const bool big_ok = fast && taps.n > 0 && (epi == 0 || epi == 1) && bnb == nullptr && pscale == nullptr &&
-                      Co >= 128;
-  const int big = big_ok ? big_tile_pick(g_tune[kTgBig], p.M, Co, taps.n, ds) : 0;
+  const bool big_ok = fast && taps.n > 0 && (epi == 0 || epi == 1) && q.bnb == nullptr && q.pscale == nullptr &&
+                      q.Co >= 128;
+  const int big = big_ok ? big_tile_pick(g_tune[kTgBig], p.M, q.Co, taps.n, q.ds) : 0;
   if (big != 0) {
     p.nkt1 = taps.n * p.cpt / 4;  // 32-deep k-tiles (cpt % 8 == 0 on FAST shapes)
     p.nkt = p.nkt1 + p.Cs2 / 32;
@@ -2338,20 +2349,21 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
   // 256-channel tiles (g_tune[kTgTileN] = 256, A/B and autotuner): each wave 64 rows x 128 channels, the
   // A tile read once per 256 output channels -- for the short-K expansion 1x1 convs, whose A reads
   // are half of their bytes at 128-channel tiles.  Plain / statistics epilogue only.
-  if (bn == 256 && !(fast && (epi == 0 || epi == 1) && pscale == nullptr && Co > 128 && src2 == nullptr)) bn = 128;
+  if (bn == 256 && !(fast && (epi == 0 || epi == 1) && q.pscale == nullptr && q.Co > 128 && q.src2 == nullptr))
+    bn = 128;
   if (bn == 256) {
     // (32-deep k-tiles only: the 64-deep variant spills at the 168-register cap)
-    const int grid256 = ntm * ((Co + 255) / 256);
+    const int grid256 = ntm * ((q.Co + 255) / 256);
     if (epi == 1) launch_tg<256, 1, true, 2, 32>(p, grid256, stream);
     else launch_tg<256, 0, true, 2, 32>(p, grid256, stream);
     return;
   }
-  const int grid = ntm * ((Co + bn - 1) / bn);
-  if (pscale != nullptr) {
+  const int grid = ntm * ((q.Co + bn - 1) / bn);
+  if (q.pscale != nullptr) {
     // BN prologue on the A operand: 1x1 / stride-1 / FAST, plain or statistics epilogue,
     // double-buffered (the per-channel table is indexed by k-tile)
-    if (!(fast && taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 && ss == 1 && ds == 1 && (epi == 0 || epi == 1) &&
-          addsrc == nullptr && aff == nullptr && bnb == nullptr)) {
+    if (!(fast && taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 && q.ss == 1 && q.ds == 1 &&
+          (epi == 0 || epi == 1) && q.addsrc == nullptr && q.aff == nullptr && q.bnb == nullptr)) {
       fprintf(stderr, "launch_tap_gemm: the BN prologue needs a plain 1x1 stride-1 forward with C %% 64 == 0\n");
       abort();
     }
@@ -2367,7 +2379,7 @@ static void tap_gemm_impl(const bf16* src, int N, int Hs, int Ws, int Cs,
 #undef DCP_TG_PRO
     return;
   }
-  if (src2 != nullptr) {
+  if (q.src2 != nullptr) {
 #define DCP_TG_S2(BN_)                                                                 \
   if (bk32 && ns == 2) launch_tg<BN_, 0, true, 2, 32, false, true>(p, grid, stream);   \
   else if (bk32 && ns == 3) launch_tg<BN_, 0, true, 3, 32, false, true>(p, grid, stream); \
@@ -2439,163 +2451,71 @@ static const TgCfg kTgCfgs[] = {
     // (the 4-wave 256 x 256 tile, g_tune[kTgBig] = 4, is not a candidate: slower on every R50 shape,
     // profiles/r4/big4_tile_ab_b1024.txt)
 };
-static std::mutex g_tg_mu;
-static std::unordered_map<std::string, int> g_tg_choice;
+static Autotuner g_tg_tuner("tap_gemm", "tg", (int)(sizeof(kTgCfgs) / sizeof(kTgCfgs[0])));
 
-struct TuneOverride {
-  static constexpr int kSlots[8] = {kTgTileN, kTgStages, kTgKDepth, kTgBig, kTgBigCvar, kTgBigSK, kTgWs, kTgPs};
-  int saved[8];
-  explicit TuneOverride(const TgCfg& c) {
-    const int v[8] = {c.bn, c.ns, c.bk, c.big, c.cvar, c.sk, c.ws, c.ps};
-    for (int i = 0; i < 8; ++i) {
-      saved[i] = g_tune[kSlots[i]];
-      g_tune[kSlots[i]] = v[i];
-    }
-  }
-  ~TuneOverride() {
-    for (int i = 0; i < 8; ++i) g_tune[kSlots[i]] = saved[i];
-  }
-};
+int tap_gemm_tuned_count() { return g_tg_tuner.size(); }
+std::string tap_gemm_tune_export() { return g_tg_tuner.export_text(); }
+int tap_gemm_tune_import(const std::string& text) { return g_tg_tuner.import_text(text); }
 
-int tap_gemm_tuned_count() {
-  std::lock_guard<std::mutex> lk(g_tg_mu);
-  return (int)g_tg_choice.size();
-}
-
-// The tuner's decisions as text ("<key>\t<choice>\n" per problem) and back: a tuning cache that
-// makes a later process run exactly the kernels an earlier one measured (DCP_TUNE_CACHE, _ext.py) --
-// reproducible kernel choices run to run, and profiles without tuning dispatches.  Keys never
-// contain tabs or newlines; entries whose choice is out of this build's candidate range are skipped.
-std::string tap_gemm_tune_export() {
-  std::lock_guard<std::mutex> lk(g_tg_mu);
-  std::string out;
-  for (const auto& kv : g_tg_choice) out += kv.first + "\t" + std::to_string(kv.second) + "\n";
-  return out;
-}
-
-int tap_gemm_tune_import(const std::string& text) {
-  const int ncfg = (int)(sizeof(kTgCfgs) / sizeof(kTgCfgs[0]));
-  std::lock_guard<std::mutex> lk(g_tg_mu);
-  int n = 0;
-  size_t pos = 0;
-  while (pos < text.size()) {
-    size_t nl = text.find('\n', pos);
-    if (nl == std::string::npos) nl = text.size();
-    const std::string line = text.substr(pos, nl - pos);
-    pos = nl + 1;
-    const size_t tab = line.rfind('\t');
-    if (tab == std::string::npos || tab == 0) continue;
-    const int c = atoi(line.c_str() + tab + 1);
-    if (c < 0 || c >= ncfg) continue;
-    g_tg_choice[line.substr(0, tab)] = c;
-    ++n;
-  }
-  return n;
-}
-
-void launch_tap_gemm(const bf16* src, int N, int Hs, int Ws, int Cs,
-                     const bf16* wt, int Co, int T,
-                     bf16* dst, int Hd, int Wd, int Hy, int Wy, int ss, int ds, int oy, int ox,
-                     const TapList& taps, float* stats, const float* bias, int relu,
-                     const bf16* zero, hipStream_t stream, const bf16* addsrc, const BnBwdEpi* bnb,
-                     const AffineEpi* aff, const float* pscale, const float* pshift, int nbias,
-                     const bf16* src2, int Cs2, const float* bias2) {
-  auto run = [&]() {
-    tap_gemm_impl(src, N, Hs, Ws, Cs, wt, Co, T, dst, Hd, Wd, Hy, Wy, ss, ds, oy, ox, taps, stats, bias, relu, zero,
-                  stream, addsrc, bnb, aff, pscale, pshift, nbias, src2, Cs2, bias2);
-  };
-  const bool fast = (Cs % 64) == 0 && taps.n <= 32;
-  // only the FAST shapes have alternatives; A/B overrides set by hand win over the tuner
-  // (an add source aliasing the output would accumulate over the timing runs: never tuned)
-  if (g_tune[kAutotune] != 1 || !fast || pscale != nullptr || g_tune[kTgTileN] || g_tune[kTgStages] || g_tune[kTgKDepth] || g_tune[kTgBig] || g_tune[kTgBigSK] || g_tune[kTgWs] || g_tune[kTgPs] ||
-      (long)N * Hy * Wy == 0 || (addsrc != nullptr && addsrc == dst)) {
-    run();
-    return;
-  }
+// the problem as the tuner's key: geometry, channels, epilogue digits, taps
+static std::string tap_gemm_key(const TapGemmProblem& q) {
+  const TapList& taps = *q.taps;
   // (the BN-backward digit: 1 recomputed mask, 2 mask bits, 3 mask bits without the BN input -- a value of
   // its own, so the keys of every other problem, and caches recorded with them, stay as they were)
   char kb[512];
-  int len = snprintf(kb, sizeof(kb), "%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d|%d%d%d%d%d%d|", N, Hs, Ws, Cs, Co,
-                     T, Hd, Wd, Hy, Wy, ss, ds, oy, ox, taps.n, stats != nullptr, bias != nullptr, relu,
-                     addsrc != nullptr, bnb ? (bnb->y == nullptr ? 3 : (bnb->mask ? 2 : 1)) : 0, aff != nullptr);
+  int len = snprintf(kb, sizeof(kb), "%d %d %d %d %d %d %d %d %d %d %d %d %d %d %d|%d%d%d%d%d%d|", q.N, q.Hs, q.Ws,
+                     q.Cs, q.Co, q.T, q.Hd, q.Wd, q.Hy, q.Wy, q.ss, q.ds, q.oy, q.ox, taps.n, q.stats != nullptr,
+                     q.bias != nullptr, q.relu, q.addsrc != nullptr,
+                     q.bnb ? (q.bnb->y == nullptr ? 3 : (q.bnb->mask ? 2 : 1)) : 0, q.aff != nullptr);
   for (int i = 0; i < taps.n && len < (int)sizeof(kb) - 16; ++i)
     len += snprintf(kb + len, sizeof(kb) - len, "%d,%d,%d;", taps.dy[i], taps.dx[i], taps.widx[i]);
   // a second source is a field of its own (single-source keys keep their form: earlier caches stay valid
   // and can never match a two-source problem)
-  if (src2 != nullptr && len < (int)sizeof(kb) - 24)
-    len += snprintf(kb + len, sizeof(kb) - len, "|s2:%d,%d", Cs2, bias2 != nullptr);
-  const std::string key(kb);
-  int choice = -1;
-  {
-    std::lock_guard<std::mutex> lk(g_tg_mu);
-    auto it = g_tg_choice.find(key);
-    if (it != g_tg_choice.end()) choice = it->second;
+  if (q.src2 != nullptr && len < (int)sizeof(kb) - 24)
+    len += snprintf(kb + len, sizeof(kb) - len, "|s2:%d,%d", q.Cs2, q.bias2 != nullptr);
+  return std::string(kb);
+}
+
+// candidates that do not apply to the problem (they would time the heuristic's kernel again, or sum in
+// another order)
+static bool tap_gemm_skip(const TapGemmProblem& q, const TgCfg& cfg) {
+  const bool big_ok = q.bnb == nullptr && q.aff == nullptr && q.bias == nullptr && q.relu == 0 && q.Co >= 128;
+  // where the 128-row kernels split K, the (unsplit) big tiles would sum another way: not candidates
+  // (those that would not split: big tiles, 128 / 256-channel tiles, the 4-stage ring)
+  const bool ksplit = q.src2 == nullptr && tg_split_slices(q.N * q.Hy * q.Wy, q.Co, q.taps->n * q.Cs) >= 2;
+  if (ksplit && (cfg.big == 1 || cfg.big == 3 || cfg.bn == 128 || cfg.bn == 256 || cfg.ns == 4 || cfg.ws == 1 ||
+                 cfg.ps != 0))
+    return true;
+  if (cfg.big == 3 && !big_ok) return true;
+  if (cfg.big == 1 && !(big_ok && q.Co >= 256)) return true;  // (the ping-pong candidate too)
+  if (cfg.bn == 256 && !(q.Co > 128 && q.bnb == nullptr && q.bias == nullptr && q.relu == 0 && q.src2 == nullptr))
+    return true;
+  if (cfg.bn == 64 && q.Co <= 64 && cfg.ns == 0) return true;  // the heuristic's tile already
+  if (cfg.ws == 1 && !ws_applies(q)) return true;
+  if (cfg.ps != 0 && !ps_applies(q)) return true;
+  return false;
+}
+
+void launch_tap_gemm(const TapGemmProblem& q, hipStream_t stream) {
+  const bool fast = (q.Cs % 64) == 0 && q.taps->n <= 32;
+  // only the FAST shapes have alternatives; A/B overrides set by hand win over the tuner
+  // (an add source aliasing the output would accumulate over the timing runs: never tuned)
+  if (g_tune[kAutotune] != 1 || !fast || q.pscale != nullptr || g_tune[kTgTileN] || g_tune[kTgStages] ||
+      g_tune[kTgKDepth] || g_tune[kTgBig] || g_tune[kTgBigSK] || g_tune[kTgWs] || g_tune[kTgPs] ||
+      (long)q.N * q.Hy * q.Wy == 0 || (q.addsrc != nullptr && q.addsrc == q.dst)) {
+    tap_gemm_impl(q, stream);
+    return;
   }
-  if (choice < 0) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-      run();  // no timing inside a capture: the heuristic (tuned on the eager warm-up steps)
-      return;
-    }
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    float best = 1e30f, t_heur = 1e30f;
-    choice = 0;
-    const bool big_ok = bnb == nullptr && aff == nullptr && bias == nullptr && relu == 0 && Co >= 128;
-    // where the 128-row kernels split K, the (unsplit) big tiles would sum another way: not candidates
-    const bool ksplit = src2 == nullptr && tg_split_slices(N * Hy * Wy, Co, taps.n * Cs) >= 2;
-    for (int c = 0; c < (int)(sizeof(kTgCfgs) / sizeof(kTgCfgs[0])); ++c) {
-      const TgCfg& cfg = kTgCfgs[c];
-      // (those that would not split: big tiles, 128 / 256-channel tiles, the 4-stage ring)
-      if (ksplit && (cfg.big == 1 || cfg.big == 3 || cfg.bn == 128 || cfg.bn == 256 || cfg.ns == 4 ||
-                     cfg.ws == 1 || cfg.ps != 0))
-        continue;
-      if (cfg.big == 3 && !big_ok) continue;
-      if (cfg.big == 1 && !(big_ok && Co >= 256)) continue;  // (the ping-pong candidate too)
-      if (cfg.bn == 256 && !(Co > 128 && bnb == nullptr && bias == nullptr && relu == 0 && src2 == nullptr)) continue;
-      if (cfg.bn == 64 && Co <= 64 && cfg.ns == 0) continue;  // the heuristic's tile already
-      if ((cfg.ws == 1 || cfg.ps != 0) && src2 != nullptr) continue;  // (single-source kernels)
-      if (cfg.ws == 1 && !(taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 && ss == 1 && ds == 1 && Hd == Hy &&
-                           Wd == Wy && Hs == Hy && Ws == Wy && T == 1 && addsrc == nullptr && aff == nullptr &&
-                           bnb == nullptr && bias == nullptr && relu == 0 &&
-                           conv1x1_ws_supported(Cs, Co, (long)N * Hy * Wy)))
-        continue;  // (the candidate would time the heuristic again)
-      if (cfg.ps != 0 && !(taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 && ss == 1 && ds == 1 && Hd == Hy &&
-                           Wd == Wy && Hs == Hy && Ws == Wy && T == 1 && addsrc == nullptr && aff == nullptr &&
-                           bnb == nullptr && bias == nullptr && relu == 0 &&
-                           conv1x1_ps_supported(Cs, Co, (long)N * Hy * Wy)))
-        continue;
-      TuneOverride ov(cfg);
-      run();  // warm
-      float t = 1e30f;
-      for (int r = 0; r < 3; ++r) {
-        hipEventRecord(e0, stream);
-        run();
-        hipEventRecord(e1, stream);
-        hipEventSynchronize(e1);
-        float ms = 0.f;
-        hipEventElapsedTime(&ms, e0, e1);
-        t = std::min(t, ms);
-      }
-      if (c == 0) {
-        t_heur = best = t;
-      } else if (t < best && t < 0.98f * t_heur) {  // must beat the heuristic by 2 % to replace it
-        best = t;
-        choice = c;
-      }
-    }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    {
-      std::lock_guard<std::mutex> lk(g_tg_mu);
-      g_tg_choice[key] = choice;
-    }
-    if (getenv("DCP_AUTOTUNE_LOG"))
-      fprintf(stderr, "[dcp-autotune] tap_gemm %s -> cfg %d (%.1f us)\n", key.c_str(), choice, best * 1e3f);
-  }
-  TuneOverride ov(kTgCfgs[choice]);
-  run();  // the outputs of the call itself (the tuning runs already wrote the same values)
+  auto run_with = [&](int c) {
+    const TgCfg& cfg = kTgCfgs[c];
+    TuneGuard ov({kTgTileN, kTgStages, kTgKDepth, kTgBig, kTgBigCvar, kTgBigSK, kTgWs, kTgPs},
+                 {cfg.bn, cfg.ns, cfg.bk, cfg.big, cfg.cvar, cfg.sk, cfg.ws, cfg.ps});
+    tap_gemm_impl(q, stream);
+  };
+  const int choice =
+      g_tg_tuner.pick(tap_gemm_key(q), stream, [&](int c) { return tap_gemm_skip(q, kTgCfgs[c]); }, run_with);
+  if (choice < 0) tap_gemm_impl(q, stream);  // a new problem inside a capture: the heuristic
+  else run_with(choice);  // the outputs of the call itself (the tuning runs already wrote the same values)
 }
 
 // Deterministic split-K reduction, two levels: a workgroup sums a chunk of up to 64
@@ -2729,7 +2649,7 @@ static int wgrad_tiles(int Co, int ldw) {
   return ((Co + bt - 1) / bt) * ((ldw + bt - 1) / bt);
 }
 
-int wgrad_splits(int M, int Co, int ldw, int taps, int num_cu, int* rows_per_split) {
+static int wgrad_splits(int M, int Co, int ldw, int taps, int num_cu, int* rows_per_split) {
   const bool big = wgrad_big(Co, ldw);
   const int tiles = wgrad_tiles(Co, ldw);
   const int per_cu = (big || wgrad_narrow(Co, ldw)) ? (big ? 1 : 2) : (taps == 1 ? 2 : 4);
@@ -2750,49 +2670,49 @@ int wgrad_splits(int M, int Co, int ldw, int taps, int num_cu, int* rows_per_spl
 }
 
 // the 3x3 / stride-1 / pad-1 same-size geometry of wgrad3x3.hip (taps in fwd_taps order)
-static bool is_3x3_same(int Ho, int Wo, int Hs, int Ws, int ss, const TapList& taps) {
-  if (taps.n != 9 || ss != 1 || Hs != Ho || Ws != Wo) return false;
+static bool is_3x3_same(const WgradProblem& q) {
+  const TapList& taps = *q.taps;
+  if (taps.n != 9 || q.ss != 1 || q.Hs != q.Ho || q.Ws != q.Wo) return false;
   for (int i = 0; i < 9; ++i)
     if (taps.dy[i] != i / 3 - 1 || taps.dx[i] != i % 3 - 1) return false;
   return true;
 }
 
-int wgrad_plan_splits(int N, int Ho, int Wo, int Co, int Hs, int Ws, int Cs, int ss, const TapList& taps,
-                      int num_cu) {
-  if (is_3x3_same(Ho, Wo, Hs, Ws, ss, taps)) {
-    const int s3 = wgrad3x3_splits(N, Ho, Wo, Cs, Co, num_cu);
+int wgrad_plan_splits(const WgradProblem& q, int num_cu) {
+  if (is_3x3_same(q)) {
+    const int s3 = wgrad3x3_splits(q.N, q.Ho, q.Wo, q.Cs, q.Co, num_cu);
     if (s3 > 0) return s3;
   }
-  return wgrad_splits(N * Ho * Wo, Co, taps.n * Cs, taps.n, num_cu, nullptr);
+  return wgrad_splits(q.N * q.Ho * q.Wo, q.Co, q.taps->n * q.Cs, q.taps->n, num_cu, nullptr);
 }
 
-void launch_wgrad(const bf16* dy, int N, int Ho, int Wo, int Co,
-                  const bf16* src, int Hs, int Ws, int Cs, int ss,
-                  const TapList& taps, float* dw, float* part, const bf16* zero, int num_cu, hipStream_t stream,
-                  const float* pscale, const float* pshift) {
+void launch_wgrad(const WgradProblem& q, float* dw, float* part, int num_cu, hipStream_t stream) {
+  const TapList& taps = *q.taps;
+  const int Co = q.Co, Cs = q.Cs;
   WgradParams p;
-  p.dy = dy; p.src = src; p.dw = dw; p.zero = zero;
-  p.pscale = pscale; p.pshift = pshift;
-  const bool pro = pscale != nullptr;
-  p.Hs = Hs; p.Ws = Ws; p.Cs = Cs; p.Ho = Ho; p.Wo = Wo; p.ss = ss;
-  p.Co = Co; p.M = N * Ho * Wo; p.ldw = taps.n * Cs;
+  p.dy = q.dy; p.src = q.src; p.dw = dw; p.zero = q.zero;
+  p.pscale = q.pscale; p.pshift = q.pshift;
+  const bool pro = q.pscale != nullptr;
+  p.Hs = q.Hs; p.Ws = q.Ws; p.Cs = Cs; p.Ho = q.Ho; p.Wo = q.Wo; p.ss = q.ss;
+  p.Co = Co; p.M = q.N * q.Ho * q.Wo; p.ldw = taps.n * Cs;
   p.cpt = Cs / 8; p.kc_total = taps.n * p.cpt;
-  p.div_wo = make_fastdiv(Wo); p.div_ho = make_fastdiv(Ho); p.div_cpt = make_fastdiv(p.cpt);
+  p.div_wo = make_fastdiv(q.Wo); p.div_ho = make_fastdiv(q.Ho); p.div_cpt = make_fastdiv(p.cpt);
   for (int i = 0; i < taps.n; ++i) {
     p.dy_t[i] = (int8_t)taps.dy[i];
     p.dx_t[i] = (int8_t)taps.dx[i];
   }
-  if (is_3x3_same(Ho, Wo, Hs, Ws, ss, taps)) {
-    const int s3 = wgrad3x3_splits(N, Ho, Wo, Cs, Co, num_cu);
+  if (is_3x3_same(q)) {
+    const int s3 = wgrad3x3_splits(q.N, q.Ho, q.Wo, Cs, Co, num_cu);
     if (s3 > 0) {
       // part holds wgrad_plan_splits(...) = s3 partial slices (the caller sized it by that plan);
       // a BN prologue is recomputed on the staged window (the 3x3 consumer's K5)
-      launch_wgrad3x3(dy, src, N, Ho, Wo, Cs, Co, part, s3, zero, stream, pscale, pshift);
+      launch_wgrad3x3(q.dy, q.src, q.N, q.Ho, q.Wo, Cs, Co, part, s3, q.zero, stream, q.pscale, q.pshift);
       launch_split_reduce(part, s3, Co * 9 * Cs, dw, stream);
       return;
     }
   }
-  p.direct = (taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 && ss == 1 && Hs == Ho && Ws == Wo) ? 1 : 0;
+  p.direct =
+      (taps.n == 1 && taps.dy[0] == 0 && taps.dx[0] == 0 && q.ss == 1 && q.Hs == q.Ho && q.Ws == q.Wo) ? 1 : 0;
   const bool big = wgrad_big(Co, p.ldw);
   const bool narrow = wgrad_narrow(Co, p.ldw);
   if (pro && (!p.direct || narrow)) {  // (the 64-row kernel has no prologue)

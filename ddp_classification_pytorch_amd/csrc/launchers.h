@@ -6,13 +6,10 @@
 
 #include <string>
 
+#include "tune.h"  // tuning switches (in-process A/B experiments, the autotuner's overrides): named slots
+
 typedef __bf16 bf16;
 
-namespace dcp {
-
-// tuning switches (in-process A/B experiments, the autotuner's overrides): named slots, tune.h
-}  // namespace dcp
-#include "tune.h"
 namespace dcp {
 
 constexpr int kMaxTaps = 64;
@@ -60,43 +57,83 @@ struct AffineEpi {
 using WorkspaceAlloc = void* (*)(size_t bytes, hipStream_t stream);
 using WorkspaceFree = void (*)(void* ptr);
 void set_workspace_allocator(WorkspaceAlloc alloc, WorkspaceFree free_fn);
+// One implicit-GEMM ("tap GEMM") launch, forward or data gradient:
+//   dst[n][oy + y*ds][ox + x*ds][co] = epilogue(sum over taps t, channels c of
+//                                      src[n][y*ss + dy_t][x*ss + dx_t][c] * wt[co][widx_t][c])
+// for the Hy x Wy output pixels (y, x) of each image; source pixels out of range read `zero`.
+struct TapGemmProblem {
+  // source [N][Hs][Ws][Cs]
+  const bf16* src = nullptr;
+  int N = 0, Hs = 0, Ws = 0, Cs = 0;
+  // weight [Co][T][Cs] (with a second source: [Co][T*Cs + Cs2])
+  const bf16* wt = nullptr;
+  int Co = 0, T = 0;
+  // destination [N][Hd][Wd][Co] and the output grid Hy x Wy computed by this launch: source stride ss,
+  // destination stride ds and offset (oy, ox) -- a stride-2 data gradient writes one parity class per launch
+  bf16* dst = nullptr;
+  int Hd = 0, Wd = 0, Hy = 0, Wy = 0, ss = 1, ds = 1, oy = 0, ox = 0;
+  const TapList* taps = nullptr;  // (read during the launch call only)
+  // epilogue: BN statistics slabs [ceil(M/128)][2][Co] of the output; bias (fp32, its first nbias columns;
+  // 0 = all Co) and relu (1 ReLU, 2 sigmoid: the linear layers); an add source shaped like dst; the fused
+  // BN backward (BnBwdEpi) or the folded eval-mode BN (AffineEpi)
+  float* stats = nullptr;
+  const float* bias = nullptr;
+  int nbias = 0, relu = 0;
+  const bf16* addsrc = nullptr;
+  const BnBwdEpi* bnb = nullptr;
+  const AffineEpi* aff = nullptr;
+  // prologue: BN + ReLU on the input of a 1x1 stride-1 forward, K5 -- the input is the BN's input x and
+  // the conv sees bf16(relu(x * pscale[c] + pshift[c]))
+  const float *pscale = nullptr, *pshift = nullptr;
+  // second source: a second A operand concatenated along K -- a 1x1 source [pixels][Cs2] on src's pixel
+  // grid, Cs2 % 64 == 0, against columns T*Cs .. of the weight; bias2, fp32 [Co], is added in fp32 before
+  // the output's bf16 rounding.  Plain FAST store GEMMs only; never split-K.
+  const bf16* src2 = nullptr;
+  int Cs2 = 0;
+  const float* bias2 = nullptr;
+  const bf16* zero = nullptr;  // >= 256 zero bytes: the source of every out-of-bounds lane
+};
+void launch_tap_gemm(const TapGemmProblem& p, hipStream_t stream);
 // number of problems the tap-GEMM autotuner (g_tune[kAutotune] = 1) has measured in this process
 int tap_gemm_tuned_count();
-// the tuner's per-problem choices as "key\tchoice" lines, and back (returns entries accepted)
+// the tuner's per-problem choices as "tg\tkey\tchoice" lines, and back: the "tg" lines of `text`
+// (returns entries accepted)
 std::string tap_gemm_tune_export();
 int tap_gemm_tune_import(const std::string& text);
-void launch_tap_gemm(const bf16* src, int N, int Hs, int Ws, int Cs, const bf16* wt, int Co, int T, bf16* dst, int Hd,
-                     int Wd, int Hy, int Wy, int ss, int ds, int oy, int ox, const TapList& taps, float* stats,
-                     const float* bias, int relu, const bf16* zero, hipStream_t stream, const bf16* addsrc = nullptr,
-                     const BnBwdEpi* bnb = nullptr, const AffineEpi* aff = nullptr,
-                     const float* pscale = nullptr, const float* pshift = nullptr, int nbias = 0,
-                     const bf16* src2 = nullptr, int Cs2 = 0, const float* bias2 = nullptr);
-// (src2, Cs2, bias2: a second A source concatenated along K -- a 1x1 source [pixels][Cs2] on src's pixel
-// grid, Cs2 % 64 == 0, against columns T*Cs .. of the weight, then a [Co][T*Cs + Cs2] matrix; bias2, fp32
-// [Co], is added in fp32 before the output's bf16 rounding.  Plain FAST store GEMMs only; never split-K.)
-// (pscale, pshift: BN + ReLU prologue on the input of a 1x1 stride-1 forward, K5 -- the input is
-// the BN's input x and the conv sees bf16(relu(x * pscale[c] + pshift[c])))
 // backward of act(c * scale + shift [+ r]) from its output y: g = dy * act'(y) and dc = g * scale
 // (g only when want_g: the residual's gradient)
 void launch_act_scale_bwd(const bf16* dy, const bf16* y, const float* scale, int64_t M, int C, int act, float slope,
                           bf16* dc, bf16* g, hipStream_t s);
 void launch_partial_sum(const float* part, int P, int K, float* out, hipStream_t s);
 void launch_partial_sum_bf16(const float* part, int P, int K, bf16* out, hipStream_t s);
-// partial-slab split-K weight gradient: dw is fully written when part != nullptr
-// (part = wgrad_splits(...) x Co x T*Cs floats); part == nullptr -> fp32 atomics into a zeroed dw
-int wgrad_splits(int M, int Co, int ldw, int taps, int num_cu, int* rows_per_split);
-// splits (partials) of launch_wgrad for this geometry: the direct 3x3 kernel's where it applies
-int wgrad_plan_splits(int N, int Ho, int Wo, int Co, int Hs, int Ws, int Cs, int ss, const TapList& taps,
-                      int num_cu);
+// Weight gradient dw[co][t][c] = sum over output pixels of dy[n][y][x][co] * src[n][y*ss + dy_t][x*ss + dx_t][c]
+struct WgradProblem {
+  // output gradient [N][Ho][Wo][Co]
+  const bf16* dy = nullptr;
+  int N = 0, Ho = 0, Wo = 0, Co = 0;
+  // conv input [N][Hs][Ws][Cs], source stride ss
+  const bf16* src = nullptr;
+  int Hs = 0, Ws = 0, Cs = 0, ss = 1;
+  const TapList* taps = nullptr;  // (read during the call only)
+  // BN + ReLU prologue on the input (as TapGemmProblem's): 1x1 stride-1, or the direct 3x3 kernel
+  const float *pscale = nullptr, *pshift = nullptr;
+  const bf16* zero = nullptr;
+};
+// splits (partials) of launch_wgrad for this problem: the direct 3x3 kernel's where it applies
+int wgrad_plan_splits(const WgradProblem& p, int num_cu);
+// floats of a split-K partial buffer for launch_split_reduce: `splits` rows of `row` floats and, behind
+// them, the ceil(splits / 64) chunk sums of its two-level reduction
+inline size_t split_part_elems(int splits, size_t row) { return (size_t)(splits + (splits + 63) / 64) * row; }
 // wgrad3x3.hip: direct 3x3 / stride-1 / pad-1 weight gradient (0 = not applicable)
 int wgrad3x3_splits(int N, int H, int W, int C, int Co, int num_cu);
 void launch_wgrad3x3(const bf16* dy, const bf16* x, int N, int H, int W, int C, int Co, float* part, int splits,
                      const bf16* zero, hipStream_t stream, const float* pscale = nullptr,
                      const float* pshift = nullptr);
 void launch_split_reduce(const float* part, int splits, int n, float* out, hipStream_t stream);
-void launch_wgrad(const bf16* dy, int N, int Ho, int Wo, int Co, const bf16* src, int Hs, int Ws, int Cs, int ss,
-                  const TapList& taps, float* dw, float* part, const bf16* zero, int num_cu, hipStream_t stream,
-                  const float* pscale = nullptr, const float* pshift = nullptr);
+// partial-slab split-K weight gradient: dw [Co][T*Cs] is fully written when part != nullptr (part:
+// split_part_elems(wgrad_plan_splits(p, num_cu), Co * T*Cs) floats); part == nullptr -> fp32 atomics into
+// a zeroed dw
+void launch_wgrad(const WgradProblem& p, float* dw, float* part, int num_cu, hipStream_t stream);
 // frag: gconv_frag_elems(...) bf16 workspace (MFMA path; may be null -> direct kernels)
 // stats (optional, [gconv_fwd_stat_blocks(M)][3][Co]): BN partials of y from the MFMA kernel's epilogue;
 // returns whether they were written (false: the direct fallback kernel ran)
@@ -319,11 +356,11 @@ void launch_warp_crop(const uint8_t* src, const int64_t* meta, const float* xf, 
                       hipStream_t s);
 void launch_act_bwd(const bf16* dy, const bf16* y, bf16* dx, size_t numel, int act, hipStream_t s);
 void launch_prefix_mask(const bf16* x, bf16* y, int B, int D, const int* keep, hipStream_t s);
-// Philox dropout (misc.hip): y = x * keep / (1 - p); keep from (seed, *offset_ptr, element index);
-// `used` (optional) receives the offset the launch drew with (for the mask-regenerating backward)
 // InplaceABN effective weight: geff = |g| + eps, rg = 1 / geff; backward out = d * sign(g)
 void launch_iabn_gamma(const float* g, float eps, float* geff, float* rg, int C, hipStream_t s);
 void launch_sign_mul(const float* d, const float* g, float* out, int C, hipStream_t s);
+// Philox dropout (misc.hip): y = x * keep / (1 - p); keep from (seed, *offset_ptr, element index);
+// `used` (optional) receives the offset the launch drew with (for the mask-regenerating backward)
 void launch_dropout(const void* x, void* y, size_t n, int is_bf16, float p, uint64_t seed, const int64_t* offset_ptr,
                     int64_t* used, hipStream_t s);
 // adaptive average pool NHWC [N,H,W,C] -> [N,OH,OW,C]; backward = true: dy [N,OH,OW,C] -> dx [N,H,W,C]
@@ -331,7 +368,6 @@ void launch_adaptive_avg(const bf16* src, bf16* dst, int N, int H, int W, int C,
                          hipStream_t s);
 void launch_nested_eval_scalar(const float* feat, const float* W, const int64_t* labels, int B, int D, int C,
                                int* counts, hipStream_t s);
-// workspace bytes of launch_nested_eval (label score chains + per-class-block rank counts)
 // weight-stationary persistent 1x1 stride-1 forward GEMM (conv_ws.hip): src [M][K], wt [Co][ldw] -> dst [M][Co]
 // (+ per-128-row slab BN statistics); K in {64, 128, 256}, Co % 128 == 0; false = unsupported
 bool conv1x1_ws_supported(int K, int Co, long M);
@@ -369,6 +405,7 @@ bool launch_arcface_fused_dw(const bf16* xn, const bf16* xnT, const bf16* wn, co
 // a rank missing for timeout_ms sets *err and poisons dst with NaN (this and every later exchange)
 bool launch_peer_exchange(const float* src, int n, float* dst, const int64_t* boxes, int* epoch, int rank, int world,
                           int slot, int mode, int* err, int timeout_ms, hipStream_t s);
+// workspace bytes of launch_nested_eval (label score chains + per-class-block rank counts)
 size_t nested_eval_workspace(int B, int D, int C);
 void launch_nested_eval(const float* feat, const float* W, const int64_t* labels, int B, int D, int C, int* counts,
                         void* ws, hipStream_t s);
