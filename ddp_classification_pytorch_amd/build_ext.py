@@ -89,7 +89,8 @@ def build_host(force: bool = False, verbose: bool = True) -> str:
         if not cxx:
             raise RuntimeError("no host C++ compiler (g++) found for the shard loader")
         tmp = LOADER_PATH + f".tmp{os.getpid()}"
-        cmd = [cxx, "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall", "-o", tmp] + srcs
+        # -ffp-contract=off: dcpl_submit_exact reproduces PIL's double arithmetic operation by operation
+        cmd = [cxx, "-O3", "-std=c++17", "-fPIC", "-shared", "-pthread", "-Wall", "-ffp-contract=off", "-o", tmp] + srcs
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"host build failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")

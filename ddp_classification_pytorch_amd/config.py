@@ -67,6 +67,10 @@ def build_parser() -> argparse.ArgumentParser:
     a("--shard-train", dest="shard_train", default=None, help="--data shards: train shard (default <folder>/train.dcps)")
     a("--shard-val", dest="shard_val", default=None, help="--data shards: val shard (default <folder>/test.dcps)")
     a("--loader-threads", dest="loader_threads", type=int, default=8, help="native shard loader host threads")
+    a("--shard-resample", dest="shard_resample", default=None, choices=["fast", "pil"],
+      help="--data shards: 'fast' (default: plain bilinear) or 'pil' (Pillow's antialiased fixed-point "
+           "resize and nearest rotation, byte for byte what build_transform gives on the same record and draws); "
+           "env DCP_SHARD_RESAMPLE when the flag is absent")
     a("--folder", default="/root/commonfile/foodH/", help="root with train/ and test/ class folders")
     a("--train-dir", "--train_dir", dest="train_dir", default=None)
     a("--val-dir", "--val_dir", dest="val_dir", default=None)
@@ -162,6 +166,10 @@ def resolve(args: argparse.Namespace) -> argparse.Namespace:
     d = WORKLOAD_DEFAULTS[args.workload]
     if getattr(args, "autotune", None) is None and os.environ.get("DCP_AUTOTUNE") in ("0", "1"):
         args.autotune = os.environ["DCP_AUTOTUNE"] == "1"  # the env switch, when no flag was given
+    if getattr(args, "shard_resample", None) is None:  # the env switch, when no flag was given
+        args.shard_resample = os.environ.get("DCP_SHARD_RESAMPLE") or "fast"
+    if args.shard_resample not in ("fast", "pil"):
+        raise ValueError(f"DCP_SHARD_RESAMPLE={args.shard_resample!r}: fast or pil")
     for k, v in d.items():
         if getattr(args, k, None) is None:
             setattr(args, k, v)

@@ -1533,6 +1533,63 @@ Tensor warp_crop(const Tensor& src, const Tensor& meta, const Tensor& xf, int64_
   return out;
 }
 
+// PIL-exact resampling.  `geo` (int32 [B][12], HOST tensor) carries each image's canvas, window
+// offset and rotation integers; what the kernels do not cover is refused here, by code.
+static const char* resample_refusal(int rc) {
+  switch (rc) {
+    case 1: return "canvas outside 1..4096";
+    case 2: return "downscale above 8x";
+    case 3: return "canvas is not the size the op was given";
+    case 4: return "window lies off the canvas";
+    default: return "output size";
+  }
+}
+
+static void check_geo(const Tensor& geo, int64_t B, const char* op) {
+  TORCH_CHECK(!geo.is_cuda() && geo.scalar_type() == at::kInt && geo.dim() == 2 && geo.size(0) == B &&
+                  geo.size(1) == 12 && geo.is_contiguous(),
+              op, " geo must be a contiguous host int32 [B, 12] tensor");
+}
+
+Tensor resample_crop(const Tensor& src, const Tensor& meta, const Tensor& geo, int64_t Ho, int64_t Wo, bool bicubic,
+                     bool canvas) {
+  check_boxes(src, meta, Ho, Wo, "resample_crop");
+  const int64_t B = meta.size(0);
+  check_geo(geo, B, "resample_crop");
+  auto out = at::empty({B, Ho, Wo, 3}, src.options());
+  auto md = meta.to(src.device(), /*non_blocking=*/meta.is_pinned());
+  auto gd = geo.to(src.device(), /*non_blocking=*/geo.is_pinned());
+  int bad = -1;
+  const int rc = dcp::launch_resample_crop(src.data_ptr<uint8_t>(), md.data_ptr<int64_t>(), gd.data_ptr<int32_t>(),
+                                           meta.data_ptr<int64_t>(), geo.data_ptr<int32_t>(), (int)B, (int)Ho,
+                                           (int)Wo, bicubic, canvas, out.data_ptr<uint8_t>(), &bad, cur_stream());
+  TORCH_CHECK(rc == 0, "resample_crop refused (code ", rc, "): ", resample_refusal(rc), ", image ", bad);
+  return out;
+}
+
+Tensor rotate_nearest_crop(const Tensor& canvas, const Tensor& meta, const Tensor& geo, int64_t Ho, int64_t Wo) {
+  CHECK_DEV(canvas);
+  CHECK_CONTIG(canvas);
+  TORCH_CHECK(canvas.scalar_type() == at::kByte && canvas.dim() == 4 && canvas.size(3) == 3,
+              "rotate_nearest_crop canvas must be uint8 [B, Sh, Sw, 3]");
+  const int64_t B = canvas.size(0);
+  TORCH_CHECK(!meta.is_cuda() && meta.scalar_type() == at::kLong && meta.dim() == 2 && meta.size(0) == B &&
+                  meta.size(1) == 8 && meta.is_contiguous(),
+              "rotate_nearest_crop meta must be a contiguous host int64 [B, 8] tensor");
+  check_geo(geo, B, "rotate_nearest_crop");
+  TORCH_CHECK(Ho > 0 && Wo > 0 && Ho <= 8192 && Wo <= 8192, "rotate_nearest_crop output size");
+  auto out = at::empty({B, Ho, Wo, 3}, canvas.options());
+  auto md = meta.to(canvas.device(), /*non_blocking=*/meta.is_pinned());
+  auto gd = geo.to(canvas.device(), /*non_blocking=*/geo.is_pinned());
+  int bad = -1;
+  const int rc = dcp::launch_rotate_nearest_crop(canvas.data_ptr<uint8_t>(), md.data_ptr<int64_t>(),
+                                                 gd.data_ptr<int32_t>(), geo.data_ptr<int32_t>(), (int)B,
+                                                 (int)canvas.size(1), (int)canvas.size(2), (int)Ho, (int)Wo,
+                                                 out.data_ptr<uint8_t>(), &bad, cur_stream());
+  TORCH_CHECK(rc == 0, "rotate_nearest_crop refused (code ", rc, "): ", resample_refusal(rc), ", image ", bad);
+  return out;
+}
+
 Tensor to_nhwc_s2d(const Tensor& src, bool nchw, double in_scale, const optional<Tensor>& mean,
                    const optional<Tensor>& stdv, int64_t block) {
   CHECK_DEV(src);
@@ -2187,6 +2244,10 @@ TORCH_LIBRARY(dcp, m) {
   m.def("to_nhwc(Tensor src, bool nchw, int cpad, float in_scale, Tensor? mean, Tensor? std) -> Tensor", &to_nhwc);
   m.def("crop_resize(Tensor src, Tensor meta, int Ho, int Wo) -> Tensor", &crop_resize);
   m.def("warp_crop(Tensor src, Tensor meta, Tensor xf, int Ho, int Wo) -> Tensor", &warp_crop);
+  m.def("resample_crop(Tensor src, Tensor meta, Tensor geo, int Ho, int Wo, bool bicubic, bool canvas) -> Tensor",
+        &resample_crop);
+  m.def("rotate_nearest_crop(Tensor canvas, Tensor meta, Tensor geo, int Ho, int Wo) -> Tensor",
+        &rotate_nearest_crop);
   m.def("to_nhwc_s2d(Tensor src, bool nchw, float in_scale, Tensor? mean, Tensor? std, int block=2) -> Tensor", &to_nhwc_s2d);
   m.def("conv_fwd_geo(Tensor x, Tensor w, int stride, int pad, int Ho, int Wo, bool stats) -> (Tensor, Tensor)",
         &conv_fwd_geo);

@@ -19,16 +19,21 @@
 //   * presets that rotate or pad (CDR/main.py:112-130, NESTED/train.py:40-45 on CIFAR,
 //     PLC/FolderDataset.py) go through dcpl_submit_affine: the same gather and box, plus one
 //     inverse-affine matrix per image that composes resize-to-canvas, rotation about the canvas
-//     centre, flip and the crop offset, resampled on the GPU by `dcp::warp_crop_kernel`.
+//     centre, flip and the crop offset, resampled on the GPU by `dcp::warp_crop_kernel`;
+//   * the opt-in `pil` resampling mode goes through dcpl_submit_exact: the same gather and draws, plus
+//     the integers of the PIL chain itself per image (canvas size, window offset, the 16.16 map of
+//     Image.rotate), for `dcp::resample_crop_kernel` / `dcp::rotate_nearest_crop_kernel`, which
+//     reproduce Pillow's resize and rotate bit for bit.
 //
 // C ABI (ctypes, see data/shards.py): dcpl_open / dcpl_close / dcpl_count / dcpl_pool_create /
-// dcpl_pool_destroy / dcpl_submit / dcpl_submit_affine / dcpl_wait.
+// dcpl_pool_destroy / dcpl_submit / dcpl_submit_affine / dcpl_submit_exact / dcpl_wait.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <deque>
 #include <fcntl.h>
@@ -80,8 +85,8 @@ struct Shard {
 };
 
 // Augmentation spec shared with Python (ctypes.Structure in data/shards.py).
-// The fields after flip_p are read by dcpl_submit_affine only; an 8-field initialiser leaves them
-// zero: no rotation, no padding, canvas = output.
+// The fields after flip_p are read by dcpl_submit_affine and dcpl_submit_exact only; an 8-field
+// initialiser leaves them zero: no rotation, no padding, canvas = output, bilinear.
 struct AugSpec {
   int32_t mode;         // 0 = RandomResizedCrop (+flip), 1 = Resize(resize)+CenterCrop(crop), 2 = whole image,
                         // 3 = RandomCrop(out, padding=pad) of the image itself, 4 = whole image stretched to the canvas
@@ -93,6 +98,7 @@ struct AugSpec {
   float rot_deg;        // RandomRotation(rot_deg) about the canvas centre; 0 = none
   int32_t pad;          // mode 3: zero padding on every side
   int32_t canvas_h, canvas_w;  // the box is resized to this canvas, the output is its centre crop; 0 = output size
+  int32_t filter;       // `pil` resampling mode, read by the device side only: 0 = bilinear, 1 = bicubic
 };
 
 // splitmix64 / counter-based stream: one independent stream per (seed, epoch, dataset index)
@@ -171,6 +177,30 @@ void affine_matrix(int h, int w, int Sh, int Sw, int out_w, double dx, double dy
   m[3] = static_cast<float>(-sa * fs * ky);
   m[4] = static_cast<float>(ca * ky);
   m[5] = static_cast<float>((cy - sa * px0 + ca * py0) * ky - 0.5);
+}
+
+// Python's round(v, 15): both it and printf/strtod round the exact binary value correctly, which
+// round(v * 1e15) / 1e15 does not always.
+double round15(double v) {
+  char buf[64];
+  snprintf(buf, sizeof(buf), "%.15f", v);
+  return std::strtod(buf, nullptr);
+}
+
+// The six 16.16 integers of PIL's Image.rotate(theta, NEAREST) on an Sh x Sw canvas, as Image.py and
+// Geometry.c compute them: output (x, y) reads canvas ((a2 + a1*y + a0*x) >> 16, (a5 + a4*y + a3*x) >> 16).
+// Every line is one double operation per operator (the library is built with -ffp-contract=off).
+void rotate_fix16(double theta, int Sh, int Sw, int32_t a[6]) {
+  double deg = std::fmod(theta, 360.0);  // Python's theta % 360.0
+  if (deg < 0.0) deg += 360.0;
+  const double ang = -(deg * (3.14159265358979323846 / 180.0));
+  const double c = round15(std::cos(ang)), s = round15(std::sin(ang));
+  const double cx = Sw / 2.0, cy = Sh / 2.0;
+  const double m2 = c * (-cx) + s * (-cy) + 0.0 + cx;
+  const double m5 = (-s) * (-cx) + c * (-cy) + 0.0 + cy;
+  auto fix = [](double v) { return static_cast<int32_t>(std::floor(v * 65536.0 + 0.5)); };
+  a[0] = fix(c), a[1] = fix(s), a[2] = fix(m2 + c * 0.5 + s * 0.5);
+  a[3] = fix(-s), a[4] = fix(c), a[5] = fix(m5 + (-s) * 0.5 + c * 0.5);
 }
 
 class Pool {
@@ -388,6 +418,65 @@ int64_t dcpl_submit_affine(void* pool, void* shard, const int64_t* indices, int 
     t[6] = theta, t[7] = 0.f;
     labels[b] = e.label;
     return rc;
+  });
+}
+
+// dcpl_submit_affine's draws for the `pil` resampling mode: the same gather, meta, labels and the
+// same draws in the same order (so a `pil` run sees the geometry a `fast` run sees), but instead of a
+// composed matrix each image gets the integers of the PIL chain itself,
+//   geo[b*12 .. b*12+12) = {Sh, Sw, dy, dx, a0, a1, a2, a3, a4, a5, rotate, angle float32 bits}:
+// resize the box to the Sh x Sw canvas (Image.resize), rotate it with the 16.16 map a0..a5 when
+// `rotate` is set (rotate_fix16), mirror, cut the out_h x out_w window at (dy, dx).  MODE_CENTER is
+// Resize(resize) + CenterCrop as data/transforms.py computes them: the box is the whole record, the
+// canvas' short side is `resize`, its long side int(round(resize * long / short)).  The pad-crop
+// (mode 3) mirrors after its crop and needs no resampling: it stays on dcpl_submit_affine (-4 here).
+// The window is centred, so it always meets its canvas.  A job fails the ticket with 6 when the box is
+// more than 8x the canvas on an axis (the filter of dcp::resample_crop_kernel stops there).
+int64_t dcpl_submit_exact(void* pool, void* shard, const int64_t* indices, int B, uint8_t* out, int64_t out_cap,
+                          int64_t* meta, int32_t* geo, int64_t* labels, const AugSpec* aug, uint64_t seed,
+                          uint64_t epoch, int out_h, int out_w) {
+  auto* s = static_cast<Shard*>(shard);
+  const uint64_t stride = s->hdr->max_bytes;
+  if (B < 0 || static_cast<uint64_t>(B) * stride > static_cast<uint64_t>(out_cap)) return -2;
+  for (int b = 0; b < B; ++b)
+    if (indices[b] < 0 || static_cast<uint64_t>(indices[b]) >= s->hdr->count) return -3;
+  AugSpec a = *aug;
+  if (out_h <= 0 || out_w <= 0 || out_h > 8192 || out_w > 8192 || a.mode < 0 || a.mode > 4 || a.mode == 3 ||
+      a.canvas_h < 0 || a.canvas_w < 0 || a.canvas_h > 4096 || a.canvas_w > 4096 || !(a.rot_deg >= 0.f) ||
+      (a.mode == 1 && (a.resize <= 0 || a.resize > 4096)))
+    return -4;
+  std::vector<int64_t> idx(indices, indices + B);
+  return static_cast<Pool*>(pool)->submit(B, [=](int b) -> int {
+    const IndexEntry& e = s->index[idx[b]];
+    const int H = static_cast<int>(e.h), W = static_cast<int>(e.w);
+    std::memcpy(out + b * stride, s->data + e.offset, size_t(H) * W * 3);
+    Rng rng(mix_key(seed, epoch, static_cast<uint64_t>(idx[b])));
+    int box[4] = {0, 0, H, W};
+    int64_t Sh = a.canvas_h > 0 ? a.canvas_h : out_h, Sw = a.canvas_w > 0 ? a.canvas_w : out_w;
+    if (a.mode == 0) rrc_box(rng, H, W, a, box);
+    if (a.mode == 1) {  // transforms.Resize(int): nearbyint rounds halves to even as Python's round does
+      const double r = a.resize;
+      if (W <= H) Sw = a.resize, Sh = static_cast<int64_t>(std::nearbyint(r * H / W));
+      else Sh = a.resize, Sw = static_cast<int64_t>(std::nearbyint(r * W / H));
+    }
+    const int64_t dy = static_cast<int64_t>(std::nearbyint((Sh - out_h) / 2.0));
+    const int64_t dx = static_cast<int64_t>(std::nearbyint((Sw - out_w) / 2.0));
+    const float theta = a.rot_deg > 0.f ? static_cast<float>((2.0 * rng.uniform() - 1.0) * a.rot_deg) : 0.f;
+    const int flip = a.mode != 1 ? rng.uniform() < a.flip_p : 0;
+    int64_t* m = meta + b * 8;
+    m[0] = static_cast<int64_t>(b * stride);
+    m[1] = H, m[2] = W, m[3] = box[0], m[4] = box[1], m[5] = box[2], m[6] = box[3], m[7] = flip;
+    labels[b] = e.label;
+    int32_t* g = geo + b * 12;
+    std::memset(g, 0, 12 * sizeof(int32_t));
+    if (Sh < 1 || Sw < 1 || Sh > 4096 || Sw > 4096) return 6;  // a record thinner than 1 / 4096 of its length
+    g[0] = static_cast<int32_t>(Sh), g[1] = static_cast<int32_t>(Sw);
+    g[2] = static_cast<int32_t>(dy), g[3] = static_cast<int32_t>(dx);
+    rotate_fix16(theta, static_cast<int>(Sh), static_cast<int>(Sw), g + 4);
+    g[10] = a.rot_deg > 0.f;
+    std::memcpy(g + 11, &theta, sizeof(float));
+    if (box[2] > 8 * Sh || box[3] > 8 * Sw) return 6;
+    return 0;
   });
 }
 

@@ -354,6 +354,16 @@ void launch_crop_resize(const uint8_t* src, const int64_t* meta, int B, int Ho, 
 // (output pixel -> box-relative source position) and fill 0 outside the box
 void launch_warp_crop(const uint8_t* src, const int64_t* meta, const float* xf, int B, int Ho, int Wo, uint8_t* out,
                       hipStream_t s);
+// PIL-exact resampling (the loader's `pil` mode): Pillow's two-pass fixed-point resize of each box
+// to its canvas, then the (mirrored-first) Ho x Wo window; geo [B][12] = {Sh, Sw, dy, dx, a0..a5,
+// rotate, angle bits}.  hmeta / hgeo are the HOST copies the refusals are decided from; the return
+// value is 0 or a refusal code with the image in *bad (resample_check in augment.hip), nothing is launched then.
+int launch_resample_crop(const uint8_t* src, const int64_t* meta, const int32_t* geo, const int64_t* hmeta,
+                         const int32_t* hgeo, int B, int Ho, int Wo, int bicubic, int whole, uint8_t* out, int* bad,
+                         hipStream_t s);
+// Image.rotate(NEAREST) through geo's 16.16 integers -> mirror -> window, of canvases [B][Sh][Sw][3]
+int launch_rotate_nearest_crop(const uint8_t* canvas, const int64_t* meta, const int32_t* geo, const int32_t* hgeo,
+                               int B, int Sh, int Sw, int Ho, int Wo, uint8_t* out, int* bad, hipStream_t s);
 void launch_act_bwd(const bf16* dy, const bf16* y, bf16* dx, size_t numel, int act, hipStream_t s);
 void launch_prefix_mask(const bf16* x, bf16* y, int B, int D, const int* keep, hipStream_t s);
 // InplaceABN effective weight: geff = |g| + eps, rg = 1 / geff; backward out = d * sign(g)

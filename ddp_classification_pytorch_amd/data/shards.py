@@ -40,6 +40,22 @@ Resize+CenterCrop is one resample of the centre box instead of two.  On the affi
 
 ``DCP_SHARD_AFFINE=0`` puts CDR, CIFAR and PLC back on the PIL DataLoader workers over the same
 shard (for A/B runs); measurements in profiles/r11/loader_affine.txt.
+
+``resample="pil"`` (``--shard-resample pil`` / ``DCP_SHARD_RESAMPLE=pil``; the default is
+``"fast"``, everything above) removes every difference listed above.  The host then draws the
+same boxes, angles and flips from the same streams but hands the device the integers of the PIL
+chain itself (``dcpl_submit_exact``: per-image canvas size, window offset, the 16.16 map of
+``Image.rotate``), and ``dcp::resample_crop`` / ``dcp::rotate_nearest_crop`` redo Pillow's
+fixed-point arithmetic: the antialiased two-pass ``resize`` (bilinear, bicubic for PLC) with its
+uint8 intermediate image, Resize(256) and CenterCrop(224) as two steps, CDR's canvas -> nearest
+rotation -> flip -> centre crop as four.  CIFAR's pad-crop was exact already and keeps the affine
+route.  What ``pil`` guarantees: for every preset, the uint8 batch equals, byte for byte, what
+``transforms.build_transform(preset)`` computes on the same shard record with the same draws
+(tests/test_resample_*.py compare with Pillow itself, no tolerance).  What it does not: the
+shard's own one-time short-side resize at packing time is still there, and the draws are this
+loader's, so a run is not equal to one that decodes the JPEGs and augments them with Python's RNG
+every epoch.  Downscales above 8x per axis (33 bicubic taps) are refused, not approximated.
+Measurements in profiles/r12/loader_exact.txt.
 """
 from __future__ import annotations
 
@@ -170,9 +186,12 @@ class AugSpec(ctypes.Structure):
     _fields_ = [("mode", ctypes.c_int32), ("resize", ctypes.c_int32), ("crop", ctypes.c_int32),
                 ("scale_lo", ctypes.c_float), ("scale_hi", ctypes.c_float),
                 ("ratio_lo", ctypes.c_float), ("ratio_hi", ctypes.c_float), ("flip_p", ctypes.c_float),
-                # read by dcpl_submit_affine only; zero (the 8-field form) = no rotation, no padding
+                # read by dcpl_submit_affine / dcpl_submit_exact only; zero (the 8-field form) = no
+                # rotation, no padding
                 ("rot_deg", ctypes.c_float), ("pad", ctypes.c_int32),
-                ("canvas_h", ctypes.c_int32), ("canvas_w", ctypes.c_int32)]
+                ("canvas_h", ctypes.c_int32), ("canvas_w", ctypes.c_int32),
+                # read by the `pil` resampling mode only: 0 = bilinear, 1 = bicubic
+                ("filter", ctypes.c_int32)]
 
     @property
     def affine(self) -> bool:
@@ -185,9 +204,22 @@ class AugSpec(ctypes.Structure):
 MODE_RRC, MODE_CENTER, MODE_WHOLE, MODE_PADCROP, MODE_STRETCH = 0, 1, 2, 3, 4
 
 
-def aug_preset(name: str, train: bool, size: int = 224):
-    """(AugSpec, output edge) of the reference transform presets (see transforms.build_transform)."""
-    name = name.lower()
+RESAMPLE_MODES = ("fast", "pil")
+
+
+def aug_preset(name: str, train: bool, size: int = 224, resample: str = "fast"):
+    """(AugSpec, output edge) of the reference transform presets (see transforms.build_transform).
+    The geometry of a preset is the same in both resampling modes; ``resample="pil"`` adds the
+    filter PIL uses (bicubic for PLC) for :class:`ShardLoader` ``(..., resample="pil")``."""
+    if resample not in RESAMPLE_MODES:
+        raise ValueError(f"shard resampling mode {resample!r}: one of {RESAMPLE_MODES}")
+    aug, out = _aug_preset(name.lower(), train, size)
+    if resample == "pil" and name.lower() == "plc":
+        aug.filter = 1  # PLC/FolderDataset.py: Resize((256, 256), BICUBIC)
+    return aug, out
+
+
+def _aug_preset(name: str, train: bool, size: int):
     if name in ("baseline", "arcface"):
         # BASELINE/main.py:58-76: train RRC(256, scale 0.8-1), no flip; val Resize(256)+CenterCrop(224)
         if train:
@@ -247,6 +279,8 @@ def native_lib():
         lib.dcpl_submit_affine.restype = i64
         lib.dcpl_submit_affine.argtypes = [vp, vp, vp, ctypes.c_int, vp, i64, vp, vp, vp, ctypes.POINTER(AugSpec),
                                            ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, ctypes.c_int]
+        lib.dcpl_submit_exact.restype = i64
+        lib.dcpl_submit_exact.argtypes = lib.dcpl_submit_affine.argtypes
         lib.dcpl_wait.restype = ctypes.c_int
         lib.dcpl_wait.argtypes = [vp, i64]
         _LIB["h"] = lib
@@ -270,13 +304,22 @@ class NativeGather:
         return int(self.lib.dcpl_count(self.shard))
 
     def submit(self, indices: torch.Tensor, out: torch.Tensor, meta: torch.Tensor, labels: torch.Tensor,
-               aug: AugSpec, seed: int, epoch: int, xf: torch.Tensor = None, out_hw=None) -> int:
+               aug: AugSpec, seed: int, epoch: int, xf: torch.Tensor = None, out_hw=None,
+               geo: torch.Tensor = None) -> int:
         """With ``xf`` (float32 [B, 8]) and ``out_hw`` the affine entry point also writes each image's
-        inverse-affine matrix; without them this is the plain crop-box call, bit for bit."""
+        inverse-affine matrix; without them this is the plain crop-box call, bit for bit.  With
+        ``geo`` (int32 [B, 12]) and ``out_hw`` it is the exact entry point of the `pil` mode: the
+        same draws, and each image's canvas, window offset and rotation integers."""
         assert indices.dtype == torch.int64 and indices.is_contiguous() and not indices.is_cuda
         B = indices.numel()
         assert meta.shape == (B, 8) and labels.shape == (B,) and out.dtype == torch.uint8
-        if xf is None:
+        if geo is not None:
+            assert geo.shape == (B, 12) and geo.dtype == torch.int32 and geo.is_contiguous() and not geo.is_cuda
+            t = self.lib.dcpl_submit_exact(self.pool, self.shard, indices.data_ptr(), B, out.data_ptr(),
+                                           out.numel(), meta.data_ptr(), geo.data_ptr(), labels.data_ptr(),
+                                           ctypes.byref(aug), int(seed) & (2**64 - 1), int(epoch),
+                                           int(out_hw[0]), int(out_hw[1]))
+        elif xf is None:
             if aug.affine:
                 raise ValueError("this AugSpec rotates, pads or stretches: submit() needs xf and out_hw")
             t = self.lib.dcpl_submit(self.pool, self.shard, indices.data_ptr(), B, out.data_ptr(), out.numel(),
@@ -320,11 +363,19 @@ class ShardLoader:
     while the caller trains on the current one.  A slot is only refilled after the side stream's
     copy out of it has completed (event per slot).  Same yield signature as
     :class:`DevicePrefetcher`, so the training loop is unchanged.
+
+    ``resample="pil"`` delivers the bytes of the PIL pipeline (module docstring) through
+    ``dcpl_submit_exact`` and the exact kernels; the pad-crop preset keeps the affine route.
+    ``tap``, when set, is called with (uint8 images, meta, xf or geo or None) of every batch before
+    normalisation: tests and tools look at the augmented bytes there.
     """
 
     def __init__(self, path: str, batch_size: int, sampler=None, aug: AugSpec = None, out_size: int = 224,
                  device="cuda", threads: int = 8, prefetch: int = 3, seed: int = 0, drop_last: bool = False,
-                 mean=IMAGENET_MEAN, std=IMAGENET_STD, cpad: int = 8, s2d=False, return_index: bool = False):
+                 mean=IMAGENET_MEAN, std=IMAGENET_STD, cpad: int = 8, s2d=False, return_index: bool = False,
+                 resample: str = "fast"):
+        if resample not in RESAMPLE_MODES:
+            raise ValueError(f"shard resampling mode {resample!r}: one of {RESAMPLE_MODES}")
         self.gather = NativeGather(path, threads)
         self.batch_size, self.sampler, self.out_size = int(batch_size), sampler, int(out_size)
         self.aug = aug if aug is not None else AugSpec(MODE_WHOLE, 0, 0, 1, 1, 1, 1, 0.0)
@@ -335,6 +386,8 @@ class ShardLoader:
         self.mean = torch.tensor(mean, dtype=torch.float32, device=self.device)
         self.std = torch.tensor(std, dtype=torch.float32, device=self.device)
         self.epoch = 0
+        self.resample, self.tap = resample, None
+        exact = resample == "pil" and self.aug.mode != MODE_PADCROP
         stride = int(self.gather.hdr["max_bytes"])
         pin = self.cuda
         nslots = self.prefetch + 1
@@ -342,7 +395,9 @@ class ShardLoader:
                            meta=torch.empty((self.batch_size, 8), dtype=torch.int64, pin_memory=pin),
                            labels=torch.empty(self.batch_size, dtype=torch.int64, pin_memory=pin),
                            xf=(torch.empty((self.batch_size, 8), dtype=torch.float32, pin_memory=pin)
-                               if self.aug.affine else None),
+                               if self.aug.affine and not exact else None),
+                           geo=(torch.empty((self.batch_size, 12), dtype=torch.int32, pin_memory=pin)
+                                if exact else None),
                            idx=None, event=None) for _ in range(nslots)]
         self.stream = torch.cuda.Stream(device=self.device) if self.cuda else None
 
@@ -374,8 +429,9 @@ class ShardLoader:
         slot["idx"] = idx
         epoch = getattr(self.sampler, "epoch", self.epoch)  # the training loop drives sampler.set_epoch
         xf = slot["xf"][:B] if slot["xf"] is not None else None
+        geo = slot["geo"][:B] if slot["geo"] is not None else None
         slot["ticket"] = self.gather.submit(idx, slot["buf"], slot["meta"][:B], slot["labels"][:B], self.aug,
-                                            self.seed, epoch, xf, (self.out_size, self.out_size))
+                                            self.seed, epoch, xf, (self.out_size, self.out_size), geo)
 
     def _convert(self, slot):
         """Join the host gather of ``slot`` and run H2D + augment + normalise (side stream)."""
@@ -387,10 +443,17 @@ class ShardLoader:
         used = min(used, slot["buf"].numel())
         src = slot["buf"][:used].to(self.device, non_blocking=True)
         labels = slot["labels"][:B].to(self.device, non_blocking=True)
-        if slot["xf"] is not None:
-            imgs = Fn.warp_crop(src, meta, slot["xf"][:B], self.out_size, self.out_size)
+        if slot["geo"] is not None:
+            extra = slot["geo"][:B]
+            imgs = Fn.resample_exact(src, meta, extra, self.out_size, self.out_size, bicubic=self.aug.filter == 1)
+        elif slot["xf"] is not None:
+            extra = slot["xf"][:B]
+            imgs = Fn.warp_crop(src, meta, extra, self.out_size, self.out_size)
         else:
+            extra = None
             imgs = Fn.crop_resize(src, meta, self.out_size, self.out_size)
+        if self.tap is not None:
+            self.tap(imgs, meta, extra)
         x = Fn.to_device_nhwc(imgs, self.mean, self.std, cpad=self.cpad, nchw=False, in_scale=1.0 / 255.0,
                               s2d=self.s2d)
         out = (x, labels)

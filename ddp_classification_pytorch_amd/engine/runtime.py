@@ -112,17 +112,19 @@ class WithIndex(torch.utils.data.Dataset):
 def _shard_loaders(args, rt, tr, va, tr_s, va_s, mean, std, cpad, s2d, drop_last_train):
     """Native loaders (C++ gather + GPU crop/resize, or the affine warp for the presets that rotate,
     pad or stretch: CDR, CIFAR, PLC).  None -- the PIL DataLoader over the same shard -- only for a
-    preset aug_preset does not know, or for those three under DCP_SHARD_AFFINE=0."""
+    preset aug_preset does not know, or for those three under DCP_SHARD_AFFINE=0.
+    ``--shard-resample pil`` runs every preset through the PIL-exact kernels instead (data/shards.py)."""
     from ..data.shards import ShardLoader, aug_preset
 
+    resample = getattr(args, "shard_resample", None) or "fast"
     try:
-        tr_aug, tr_size = aug_preset(args.transform, True, args.image_size)
-        va_aug, va_size = aug_preset(args.transform, False, args.image_size)
+        tr_aug, tr_size = aug_preset(args.transform, True, args.image_size, resample=resample)
+        va_aug, va_size = aug_preset(args.transform, False, args.image_size, resample=resample)
     except ValueError:
         return None
     idx = args.workload == "plc"
     kw = dict(device=rt.device, threads=args.loader_threads, seed=args.seed, mean=mean, std=std, cpad=cpad,
-              return_index=idx)
+              return_index=idx, resample=resample)
     tr_l = ShardLoader(tr.path, args.batchsize, tr_s, tr_aug, tr_size, drop_last=drop_last_train,
                        s2d=s2d, **kw)
     va_l = ShardLoader(va.path, args.batchsize, va_s, va_aug, va_size, s2d=s2d, **kw)

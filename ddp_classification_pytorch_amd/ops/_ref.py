@@ -534,6 +534,147 @@ def warp_crop(src, meta, xf, Ho, Wo):
     return out
 
 
+# PIL-exact resampling (resample_crop_kernel / rotate_nearest_crop_kernel in csrc/augment.hip).
+# geo rows, int32 [B, 12]: {Sh, Sw, dy, dx, a0, a1, a2, a3, a4, a5, rotate, angle float32 bits}.
+RESAMPLE_MAX_SCALE = 8  # per axis; bicubic then has 33 taps
+PIL_PRECISION_BITS = 22
+
+
+def pil_coeffs(in_size: int, out_size: int, bicubic: bool) -> torch.Tensor:
+    """Pillow's integer filter bank of one resize axis as a dense int64 [out_size, in_size] matrix
+    (zero outside each row's taps): double arithmetic, normalised, scaled by 2^22 and rounded
+    half away from zero.  Every product and sum is its own rounded double operation."""
+    scale = torch.tensor(float(in_size), dtype=torch.float64) / float(out_size)
+    fs = scale.clamp_min(1.0)
+    support = (2.0 if bicubic else 1.0) * fs
+    center = (torch.arange(out_size, dtype=torch.float64) + 0.5) * scale
+    xmin = (center - support + 0.5).long().clamp_min(0)            # truncating casts of non-negative
+    xmax = (center + support + 0.5).long().clamp_max(in_size)      # values or of values clamped to 0
+    x = torch.arange(in_size, dtype=torch.int64).view(1, -1)
+    taps = (x >= xmin.view(-1, 1)) & (x < xmax.view(-1, 1))
+    t = ((x.double() - center.view(-1, 1) + 0.5) * (1.0 / fs)).abs()
+    if bicubic:
+        a = -0.5
+        k = torch.where(t < 1.0, ((a + 2.0) * t - (a + 3.0)) * t * t + 1.0,
+                        torch.where(t < 2.0, (((t - 5.0) * t + 8.0) * t - 4.0) * a, torch.zeros_like(t)))
+    else:
+        k = torch.where(t < 1.0, 1.0 - t, torch.zeros_like(t))
+    k = torch.where(taps, k, torch.zeros_like(k))
+    ww = torch.zeros(out_size, dtype=torch.float64)
+    for j in range(int((xmax - xmin).max())):                      # accumulated in tap order, as PIL does
+        col = (xmin + j).clamp_max(in_size - 1)
+        ww = ww + torch.where(xmin + j < xmax, k.gather(1, col.view(-1, 1)).view(-1), torch.zeros_like(ww))
+    k = torch.where((ww != 0).view(-1, 1), k / ww.view(-1, 1), k)
+    scaled = k * float(1 << PIL_PRECISION_BITS)
+    return torch.where(k < 0, scaled - 0.5, scaled + 0.5).long()   # .long() truncates toward zero
+
+
+def _pil_pass(img: torch.Tensor, K: torch.Tensor) -> torch.Tensor:
+    """One resize pass along dim 0 of int64 ``img`` [n_in, ...] with the bank ``K`` [n_out, n_in]:
+    2^21 + sum, arithmetic shift by 22, clamp to uint8 range."""
+    acc = torch.tensordot(K, img, dims=([1], [0])) + (1 << (PIL_PRECISION_BITS - 1))
+    return (acc >> PIL_PRECISION_BITS).clamp(0, 255)
+
+
+def pil_resize(img: torch.Tensor, Sh: int, Sw: int, bicubic: bool) -> torch.Tensor:
+    """``Image.resize((Sw, Sh), BILINEAR | BICUBIC)`` of a uint8 [h, w, C] tensor, bit for bit: the
+    horizontal pass, rounded to uint8, then the vertical pass."""
+    h, w = int(img.shape[0]), int(img.shape[1])
+    x = img.long()
+    x = _pil_pass(x.transpose(0, 1), pil_coeffs(w, Sw, bicubic)).transpose(0, 1)
+    x = _pil_pass(x, pil_coeffs(h, Sh, bicubic))
+    return x.to(torch.uint8)
+
+
+def pil_rotate_fix16(theta: float, Sh: int, Sw: int):
+    """The six 16.16 integers (a0..a5) of ``Image.rotate(theta, NEAREST)`` on an Sh x Sw canvas:
+    output (x, y) reads canvas ((a2 + a1*y + a0*x) >> 16, (a5 + a4*y + a3*x) >> 16)."""
+    ang = -math.radians(float(theta) % 360.0)
+    c, s = round(math.cos(ang), 15), round(math.sin(ang), 15)
+    cx, cy = Sw / 2.0, Sh / 2.0
+    m2 = c * (-cx) + s * (-cy) + 0.0 + cx
+    m5 = -s * (-cx) + c * (-cy) + 0.0 + cy
+
+    def fix(v):
+        return int(math.floor(v * 65536.0 + 0.5))
+
+    return fix(c), fix(s), fix(m2 + c * 0.5 + s * 0.5), fix(-s), fix(c), fix(m5 + (-s) * 0.5 + c * 0.5)
+
+
+def _window(canvas: torch.Tensor, dy: int, dx: int, Ho: int, Wo: int, flip: bool) -> torch.Tensor:
+    """``Image.crop`` of the (mirrored first, if ``flip``) canvas: zero outside it."""
+    Sh, Sw = int(canvas.shape[0]), int(canvas.shape[1])
+    if flip:
+        canvas = canvas.flip(1)
+    out = torch.zeros((Ho, Wo, canvas.shape[2]), dtype=canvas.dtype)
+    ya, yb, xa, xb = max(dy, 0), min(dy + Ho, Sh), max(dx, 0), min(dx + Wo, Sw)
+    if ya < yb and xa < xb:
+        out[ya - dy:yb - dy, xa - dx:xb - dx] = canvas[ya:yb, xa:xb]
+    return out
+
+
+def check_resample(meta, geo, Ho, Wo, canvas):
+    """The argument checks of the exact ops (csrc/bindings.cpp:check_resample): box scale within
+    1/8 .. any, canvases within the kernels' range, window and canvas not disjoint."""
+    B = meta.shape[0]
+    if geo.shape != (B, 12) or geo.dtype != torch.int32:
+        raise RuntimeError("resample geo must be an int32 [B, 12] tensor")
+    for b in range(B):
+        h, w = int(meta[b, 5]), int(meta[b, 6])
+        Sh, Sw, dy, dx = (int(v) for v in geo[b, :4].tolist())
+        if not (0 < Sh <= 4096 and 0 < Sw <= 4096):
+            raise RuntimeError(f"resample: canvas of image {b} outside 1..4096")
+        if h > RESAMPLE_MAX_SCALE * Sh or w > RESAMPLE_MAX_SCALE * Sw:
+            raise RuntimeError(f"resample: image {b} is downscaled by more than {RESAMPLE_MAX_SCALE}x")
+        if canvas:
+            if (Sh, Sw) != (Ho, Wo):
+                raise RuntimeError(f"resample: canvas of image {b} is not the output size")
+        elif dy >= Sh or dx >= Sw or dy + Ho <= 0 or dx + Wo <= 0:
+            raise RuntimeError(f"resample: window of image {b} lies off its canvas")
+
+
+def resample_crop(src, meta, geo, Ho, Wo, bicubic, canvas):
+    """PIL's two-pass ``resize`` of each crop box to its Sh x Sw canvas (``geo`` rows), then the
+    Ho x Wo window at (dy, dx) of the canvas mirrored first when meta[7] is set, zero where the
+    window leaves the canvas.  ``canvas=True`` returns the whole canvases (Sh x Sw = Ho x Wo for
+    every image; offset and flip are left to :func:`rotate_nearest_crop`)."""
+    check_resample(meta, geo, Ho, Wo, canvas)
+    B = meta.shape[0]
+    out = torch.empty((B, Ho, Wo, 3), dtype=torch.uint8, device=src.device)
+    for b in range(B):
+        off, H, W, y0, x0, h, w, flip = (int(v) for v in meta[b].tolist())
+        Sh, Sw, dy, dx = (int(v) for v in geo[b, :4].tolist())
+        box = src[off:off + H * W * 3].view(H, W, 3)[y0:y0 + h, x0:x0 + w]
+        cv = pil_resize(box, Sh, Sw, bool(bicubic))
+        out[b] = cv if canvas else _window(cv, dy, dx, Ho, Wo, bool(flip))
+    return out
+
+
+def rotate_nearest_crop(canvas, meta, geo, Ho, Wo):
+    """``Image.rotate(theta, NEAREST)`` of each canvas [B, Sh, Sw, 3] through the 16.16 integers in
+    ``geo``, then mirror (meta[7]), then the Ho x Wo window at (dy, dx); zero outside."""
+    B, Sh, Sw = int(canvas.shape[0]), int(canvas.shape[1]), int(canvas.shape[2])
+    if geo.shape != (B, 12) or geo.dtype != torch.int32 or meta.shape[0] != B:
+        raise RuntimeError("rotate_nearest_crop geo must be an int32 [B, 12] tensor")
+    out = torch.empty((B, Ho, Wo, 3), dtype=torch.uint8, device=canvas.device)
+    y = torch.arange(Sh, dtype=torch.int64).view(-1, 1)
+    x = torch.arange(Sw, dtype=torch.int64).view(1, -1)
+    for b in range(B):
+        g = [int(v) for v in geo[b].tolist()]
+        if (g[0], g[1]) != (Sh, Sw):
+            raise RuntimeError(f"rotate_nearest_crop: geo of image {b} does not describe the canvas")
+        if g[2] >= Sh or g[3] >= Sw or g[2] + Ho <= 0 or g[3] + Wo <= 0:
+            raise RuntimeError(f"rotate_nearest_crop: window of image {b} lies off its canvas")
+        a0, a1, a2, a3, a4, a5 = g[4:10]
+        xin = (a2 + a1 * y + a0 * x) >> 16
+        yin = (a5 + a4 * y + a3 * x) >> 16
+        ok = (xin >= 0) & (xin < Sw) & (yin >= 0) & (yin < Sh)
+        rot = canvas[b][yin.clamp(0, Sh - 1), xin.clamp(0, Sw - 1)]
+        rot = torch.where(ok.unsqueeze(-1), rot, torch.zeros_like(rot))
+        out[b] = _window(rot, g[2], g[3], Ho, Wo, bool(int(meta[b, 7])))
+    return out
+
+
 def to_nhwc_s2d(src, nchw, in_scale, mean, std, block=2):
     cq = 4 if block == 2 else 3
     x = to_nhwc(src, nchw, cq, in_scale, mean, std)

@@ -1849,6 +1849,45 @@ def warp_crop(src: torch.Tensor, meta: torch.Tensor, xf: torch.Tensor, Ho: int, 
     return K(src).warp_crop(src, meta, xf, int(Ho), int(Wo))
 
 
+def resample_crop(src: torch.Tensor, meta: torch.Tensor, geo: torch.Tensor, Ho: int, Wo: int,
+                  bicubic: bool = False, canvas: bool = False) -> torch.Tensor:
+    """:func:`crop_resize` in Pillow's arithmetic, bit for bit: each box is resampled to its own
+    Sh x Sw canvas as ``Image.resize`` does (antialiased two-pass fixed point, bilinear or
+    ``bicubic``), mirrored when meta[7] is set, and the Ho x Wo window at (dy, dx) is cut from it,
+    0 where it leaves the canvas.  Host int32 ``geo`` [B, 12] = {Sh, Sw, dy, dx, a0..a5, rotate,
+    angle float32 bits}.  ``canvas=True`` returns the whole canvases (all Ho x Wo) for
+    :func:`rotate_nearest_crop`.  Downscales above 8x per axis are refused."""
+    return K(src).resample_crop(src, meta, geo, int(Ho), int(Wo), bool(bicubic), bool(canvas))
+
+
+def rotate_nearest_crop(canvas: torch.Tensor, meta: torch.Tensor, geo: torch.Tensor, Ho: int, Wo: int) -> torch.Tensor:
+    """``Image.rotate(theta, NEAREST)`` -> mirror (meta[7]) -> Ho x Wo window at (dy, dx) of uint8
+    canvases [B, Sh, Sw, 3], through the 16.16 integers a0..a5 of ``geo`` (see :func:`resample_crop`)."""
+    return K(canvas).rotate_nearest_crop(canvas, meta, geo, int(Ho), int(Wo))
+
+
+# images whose whole canvases exist at once in resample_exact's rotate chain: 100 MB of 256 x 256 canvases
+ROTATE_CHUNK = 512
+
+
+def resample_exact(src: torch.Tensor, meta: torch.Tensor, geo: torch.Tensor, Ho: int, Wo: int,
+                   bicubic: bool = False) -> torch.Tensor:
+    """The whole `pil` chain of the shard loader: resample, then -- when ``geo`` asks for the rotate
+    step (column 10; all rows alike, canvases uniform) -- the nearest rotation on the canvases,
+    ``ROTATE_CHUNK`` images at a time so that a batch of 4096 does not hold 4096 canvases."""
+    rot = geo[:, 10]
+    if geo.shape[0] and bool(rot.any()):
+        if not bool(rot.all()) or not bool((geo[:, :2] == geo[0, :2]).all()):
+            raise ValueError("resample_exact: the rotate step needs one canvas size and every row rotating")
+        Sh, Sw = int(geo[0, 0]), int(geo[0, 1])
+        parts = [rotate_nearest_crop(resample_crop(src, meta[i:i + ROTATE_CHUNK], geo[i:i + ROTATE_CHUNK], Sh, Sw,
+                                                   bicubic, True),
+                                     meta[i:i + ROTATE_CHUNK], geo[i:i + ROTATE_CHUNK], Ho, Wo)
+                 for i in range(0, geo.shape[0], ROTATE_CHUNK)]
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+    return resample_crop(src, meta, geo, Ho, Wo, bicubic, False)
+
+
 # ----------------------------------------------------------------------------- space-to-depth stem
 def nhwc_to_s2d(x: torch.Tensor) -> torch.Tensor:
     """[N, H, W, C>=4] NHWC image activations (channels >= 3 zero) -> [N, H/2, W/2, 16]."""

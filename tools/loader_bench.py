@@ -8,6 +8,8 @@ NHWC (s2d stem layout) delivered to cuda:0.  Prints one JSON line.
 augmentation instead; ``cifar`` packs 32x32 records and uses the CIFAR stem layout (no s2d).
 ``--pil-workers N`` times the path those presets had before (and keep under DCP_SHARD_AFFINE=0):
 N PIL DataLoader worker processes over the same shard feeding the device prefetcher.
+``--resample pil`` times the PIL-exact mode of the native loader (antialiased fixed-point resize,
+nearest rotation: the bytes the PIL workers deliver) instead of the default ``fast`` one.
 """
 import argparse
 import json
@@ -35,6 +37,7 @@ def main():
     ap.add_argument("--dir", default=tempfile.gettempdir())
     ap.add_argument("--preset", default="nested", choices=["nested", "cdr", "cifar", "plc"])
     ap.add_argument("--pil-workers", type=int, default=0, help="time the PIL DataLoader path with N workers instead")
+    ap.add_argument("--resample", default="fast", choices=["fast", "pil"], help="native loader resampling mode")
     a = ap.parse_args()
     rng = np.random.default_rng(0)
     path = os.path.join(a.dir, f"loader_bench_{os.getpid()}.dcps")
@@ -51,7 +54,7 @@ def main():
     write_shard(path, gen())
     pack_s = time.time() - t0
     try:
-        aug, size = aug_preset(a.preset, train=True, size=224)
+        aug, size = aug_preset(a.preset, train=True, size=224, resample=a.resample)
         sampler = ShardSampler(list(range(a.images)), num_replicas=1, rank=0, shuffle=True)
         if a.pil_workers:
             ds = ShardDataset(path, build_transform(a.preset, True, size))
@@ -60,7 +63,8 @@ def main():
             ld.set_epoch, ld.close = sampler.set_epoch, lambda: None
         else:
             ld = ShardLoader(path, a.batch, sampler=sampler, aug=aug, out_size=size, device="cuda",
-                             threads=a.threads, prefetch=a.prefetch, s2d=a.preset != "cifar", drop_last=True)
+                             threads=a.threads, prefetch=a.prefetch, s2d=a.preset != "cifar", drop_last=True,
+                             resample=a.resample)
         ld.set_epoch(0)
         for _ in ld:  # warm-up epoch (page cache, allocator)
             pass
@@ -77,10 +81,12 @@ def main():
         os.remove(path)
     what = {"nested": "RRC224+flip, bf16 NHWC s2d", "cdr": "RRC256+rot15+flip+crop224, bf16 NHWC s2d",
             "cifar": "pad4 crop32+flip, bf16 NHWC", "plc": "stretch256+flip+crop224, bf16 NHWC s2d"}[a.preset]
-    path_name = f"PIL DataLoader x{a.pil_workers} over the shard" if a.pil_workers else "shard loader"
+    path_name = (f"PIL DataLoader x{a.pil_workers} over the shard" if a.pil_workers
+                 else "shard loader" + (" (pil-exact resampling)" if a.resample == "pil" else ""))
     print(json.dumps({"metric": f"{path_name} images/s to cuda:0 ({what})",
                       "value": round(n / dt, 1), "images": a.images, "batch": a.batch, "threads": a.threads,
-                      "prefetch": a.prefetch, "pack_s": round(pack_s, 2)}), flush=True)
+                      "prefetch": a.prefetch, "resample": "PIL" if a.pil_workers else a.resample,
+                      "pack_s": round(pack_s, 2)}), flush=True)
 
 
 if __name__ == "__main__":
