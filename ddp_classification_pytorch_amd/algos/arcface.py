@@ -21,7 +21,7 @@ from ..engine.runtime import build_data, setup
 from ..models import build_model
 from ..models.heads import ArcMarginProduct, MLPHead
 from ..ops import functional as Fn
-from ..optim import StepLR, build_optimizer
+from ..optim import StepLR, build_optimizer, optimizer_flags
 from ..parallel.ddp import attach_optimizer, wrap_ddp
 
 
@@ -56,10 +56,8 @@ def run(args):
     net = wrap_ddp(model, rt.local_rank, syncbn=args.syncbn and (rt.world > 1 or args.force_ddp), bucket_cap_mb=args.bucket_cap_mb,
                    first_bucket_mb=args.first_bucket_mb, force=args.force_ddp)
     name = args.optimizer.lower()
-    wd = args.weight_decay if name in ("sgd", "lars") else 0.0  # ARCFACE/arc_main.py:249-253
-    opt = build_optimizer(name, model.parameters(), args.lr, args.momentum, wd,
-                          lars_eta=getattr(args, "lars_eta", 1e-3), lars_eps=getattr(args, "lars_eps", 1e-8),
-                          lars_keep_1d=getattr(args, "lars_keep_1d", False))
+    wd = args.weight_decay if name in ("sgd", "lars", "lamb") else 0.0  # ARCFACE/arc_main.py:249-253
+    opt = build_optimizer(name, model.parameters(), args.lr, args.momentum, wd, **optimizer_flags(args))
     attach_optimizer(net, opt)
     sched = StepLR(opt, step_size=args.step_size, gamma=args.gamma)
 

@@ -13,7 +13,7 @@ from ..engine.runtime import build_data, setup
 from ..models import build_model
 from ..models.heads import ClassifierModel, MLPHead
 from ..ops import functional as Fn
-from ..optim import StepLR, build_optimizer
+from ..optim import StepLR, build_optimizer, optimizer_flags
 from ..parallel.ddp import attach_optimizer, wrap_ddp
 
 
@@ -42,8 +42,7 @@ def run(args):
     net = wrap_ddp(model, rt.local_rank, syncbn=args.syncbn and (rt.world > 1 or args.force_ddp), bucket_cap_mb=args.bucket_cap_mb,
                    first_bucket_mb=args.first_bucket_mb, force=args.force_ddp)
     opt = build_optimizer(args.optimizer, model.parameters(), args.lr, args.momentum, args.weight_decay,
-                          args.nesterov, lars_eta=getattr(args, "lars_eta", 1e-3),
-                          lars_eps=getattr(args, "lars_eps", 1e-8), lars_keep_1d=getattr(args, "lars_keep_1d", False))
+                          args.nesterov, **optimizer_flags(args))
     attach_optimizer(net, opt)  # multi-GPU: the step runs per gradient bucket behind its all-reduce
     sched = StepLR(opt, step_size=args.step_size, gamma=args.gamma)
     C = args.num_classes

@@ -96,13 +96,23 @@ def build_parser() -> argparse.ArgumentParser:
     a("--lr", type=float, default=None)
     a("--momentum", type=float, default=None)
     a("--weight-decay", "--weight_decay", "--weightDecay", dest="weight_decay", type=float, default=None)
-    a("--optimizer", default=None, help="SGD | Adam | AdamW | LARS")
+    a("--optimizer", default=None, help="SGD | Adam | AdamW | LARS | LAMB")
     a("--nesterov", action="store_true")
     a("--lars-eta", dest="lars_eta", type=float, default=1e-3, help="LARS trust coefficient")
     a("--lars-eps", dest="lars_eps", type=float, default=1e-8, help="added to the trust ratio's denominator")
     a("--lars-keep-1d", dest="lars_keep_1d", action="store_true",
       help="LARS: adapt (and decay) BN scales / shifts and biases too, instead of stepping them with plain "
            "momentum SGD without weight decay")
+    a("--lamb-eps", dest="lamb_eps", type=float, default=1e-6, help="LAMB: added to sqrt(v) in the Adam ratio")
+    a("--lamb-no-bias-correction", dest="lamb_bias_correction", action="store_false", default=True,
+      help="LAMB: leave the moments uncorrected (bc1 = bc2 = 1)")
+    a("--lamb-keep-1d", dest="lamb_keep_1d", action="store_true",
+      help="LAMB: adapt (and decay) BN scales / shifts and biases too, instead of stepping them with trust 1 "
+           "and no weight decay")
+    a("--device-lr", dest="device_lr", action="store_true",
+      help="SGD / Adam / AdamW: the kernels read the learning rate from a device scalar, so one captured HIP "
+           "graph follows warm-up, --lr-decay poly and the epoch scheduler without recapture (LARS and LAMB "
+           "always do)")
     a("--lr-decay", dest="lr_decay", default="none", choices=["none", "poly"],
       help="poly: after --warmup-iters, lr = target * (1 - (step - warm) / (total - warm))^2 per iteration, in "
            "place of the per-epoch scheduler")

@@ -2065,11 +2065,18 @@ void mt_lars(const Tensor& table, const Tensor& chunks, const c10::optional<Tens
 // step_dev (optional int32[1] on the device): the step count the bias corrections use, read by
 // the kernel -- a HIP-graph replay then applies the current step's correction, not the captured one
 void mt_adam(const Tensor& table, const Tensor& chunks, double lr, double beta1, double beta2, double eps, double wd,
-             int64_t step, bool decoupled, double grad_scale, const c10::optional<Tensor>& step_dev) {
+             int64_t step, bool decoupled, double grad_scale, const c10::optional<Tensor>& step_dev,
+             const c10::optional<Tensor>& lr_dev) {
   CHECK_DEV(table);
   CHECK_DEV(chunks);
   dcp::AdamHyper h;
   h.step_dev = nullptr;
+  h.lr_dev = nullptr;
+  if (lr_dev.has_value() && lr_dev->defined()) {
+    CHECK_DEV((*lr_dev));
+    TORCH_CHECK(lr_dev->scalar_type() == at::kFloat && lr_dev->numel() == 1, "mt_adam: lr_dev float32[1]");
+    h.lr_dev = lr_dev->data_ptr<float>();
+  }
   if (step_dev.has_value() && step_dev->defined()) {
     CHECK_DEV((*step_dev));
     TORCH_CHECK(step_dev->scalar_type() == at::kInt && step_dev->numel() == 1, "mt_adam: step_dev int32[1]");
@@ -2090,6 +2097,66 @@ void mt_adam(const Tensor& table, const Tensor& chunks, double lr, double beta1,
   h.decoupled = decoupled ? 1 : 0;
   dcp::launch_mt_adam(reinterpret_cast<const dcp::MTEntry*>(table.data_ptr()),
                       reinterpret_cast<const int2*>(chunks.data_ptr()), chunks.size(0), h, cur_stream());
+}
+
+// LAMB.  spans / partials / trust as in mt_lars (without them the group is not adaptive: one launch,
+// every ratio 1); step_dev as in mt_adam; lr_dev (optional float32[1]): the learning rate.
+void mt_lamb(const Tensor& table, const Tensor& chunks, const c10::optional<Tensor>& spans,
+             const c10::optional<Tensor>& partials, const c10::optional<Tensor>& trust, double lr, double beta1,
+             double beta2, double eps, double wd, int64_t step, bool bias_correction, double grad_scale,
+             const c10::optional<Tensor>& step_dev, const c10::optional<Tensor>& lr_dev) {
+  CHECK_DEV(table);
+  CHECK_DEV(chunks);
+  dcp::LambHyper h;
+  h.step_dev = nullptr;
+  h.lr_dev = nullptr;
+  h.trust = nullptr;
+  if (step_dev.has_value() && step_dev->defined()) {
+    CHECK_DEV((*step_dev));
+    TORCH_CHECK(step_dev->scalar_type() == at::kInt && step_dev->numel() == 1, "mt_lamb: step_dev int32[1]");
+    h.step_dev = step_dev->data_ptr<int>();
+  }
+  if (lr_dev.has_value() && lr_dev->defined()) {
+    CHECK_DEV((*lr_dev));
+    TORCH_CHECK(lr_dev->scalar_type() == at::kFloat && lr_dev->numel() == 1, "mt_lamb: lr_dev float32[1]");
+    h.lr_dev = lr_dev->data_ptr<float>();
+  }
+  const int2* sp = nullptr;
+  float2* part = nullptr;
+  float* tr = nullptr;
+  const int64_t n = table.size(0), k = chunks.size(0);
+  if (trust.has_value() && trust->defined()) {
+    TORCH_CHECK(spans.has_value() && spans->defined() && partials.has_value() && partials->defined(),
+                "mt_lamb: an adaptive step needs spans, partials and trust");
+    CHECK_DEV((*spans));
+    CHECK_DEV((*partials));
+    CHECK_DEV((*trust));
+    TORCH_CHECK(spans->scalar_type() == at::kInt && spans->is_contiguous() && spans->numel() == 2 * n,
+                "mt_lamb: spans int32 [n,2]");
+    TORCH_CHECK(partials->scalar_type() == at::kFloat && partials->is_contiguous() && partials->numel() >= 2 * k,
+                "mt_lamb: partials float [k,2]");
+    TORCH_CHECK(trust->scalar_type() == at::kFloat && trust->is_contiguous() && trust->numel() >= n,
+                "mt_lamb: trust float [n]");
+    sp = reinterpret_cast<const int2*>(spans->data_ptr());
+    part = reinterpret_cast<float2*>(partials->data_ptr());
+    tr = trust->data_ptr<float>();
+  }
+  h.lr = lr;
+  h.beta1 = beta1;
+  h.beta2 = beta2;
+  h.eps = eps;
+  h.wd = wd;
+  h.grad_scale = grad_scale;
+  h.bias_correction = bias_correction ? 1 : 0;
+  h.bc1 = bias_correction ? 1.0 - std::pow(beta1, (double)step) : 1.0;
+  h.bc2 = bias_correction ? 1.0 - std::pow(beta2, (double)step) : 1.0;
+  h.omb1 = 1.0 - beta1;
+  h.omb2 = 1.0 - beta2;
+  h.lb1 = std::log(beta1);
+  h.lb2 = std::log(beta2);
+  dcp::launch_mt_lamb(reinterpret_cast<const dcp::MTEntry*>(table.data_ptr()),
+                      reinterpret_cast<const int2*>(chunks.data_ptr()), (int)k, sp, (int)n, part, tr, h,
+                      cur_stream());
 }
 
 // state int32 [4] = (prefix, mask, k, thr_bits) prepared by the caller; returns the threshold (fp32 GPU scalar)
@@ -2313,8 +2380,13 @@ TORCH_LIBRARY(dcp, m) {
       &mt_sgd);
   m.def(
       "mt_adam(Tensor table, Tensor chunks, float lr, float beta1, float beta2, float eps, float wd, int step, bool "
-      "decoupled, float grad_scale, Tensor? step_dev=None) -> ()",
+      "decoupled, float grad_scale, Tensor? step_dev=None, Tensor? lr_dev=None) -> ()",
       &mt_adam);
+  m.def(
+      "mt_lamb(Tensor table, Tensor chunks, Tensor? spans, Tensor? partials, Tensor? trust, float lr, float beta1, "
+      "float beta2, float eps, float wd, int step, bool bias_correction, float grad_scale, Tensor? step_dev=None, "
+      "Tensor? lr_dev=None) -> ()",
+      &mt_lamb);
   m.def(
       "mt_lars(Tensor table, Tensor chunks, Tensor? spans, Tensor? partials, Tensor? trust, float lr, float momentum, "
       "float dampening, float wd, bool nesterov, bool first, float grad_scale, float eta, float eps, Tensor? "

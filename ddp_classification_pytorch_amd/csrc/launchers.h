@@ -301,11 +301,21 @@ struct AdamHyper {
   float omb1, omb2, lb1, lb2;
   int decoupled;
   const int* step_dev;  // optional device step count: bc1/bc2 computed in-kernel from it
+  const float* lr_dev;  // optional device learning rate, read by the kernel instead of lr
 };
 struct LarsHyper {
   SgdHyper sgd;         // wd and grad_scale enter the scaled gradient d; the SGD update on d has no decay
   const float* trust;   // per table entry, or null: every trust ratio is 1 (a non-adaptive group)
   const float* lr_dev;  // optional device learning rate, read by the kernel instead of sgd.lr
+};
+struct LambHyper {
+  float lr, beta1, beta2, eps, wd, grad_scale;
+  float bc1, bc2;          // 1 - beta^step from the host (1 without bias correction); replaced in-kernel
+  float omb1, omb2, lb1, lb2;  // as in AdamHyper
+  int bias_correction;
+  const int* step_dev;     // optional device step count (bias corrections of a replayed HIP graph)
+  const float* lr_dev;     // optional device learning rate
+  const float* trust;      // per table entry; set by launch_mt_lamb
 };
 // mode: bit 0 = source bf16, bit 1 = destination bf16 (MTEntry.p = destination, .g = source)
 void launch_mt_copy(const MTEntry* tab, const int2* chunks, int nchunks, float scale, int mode, hipStream_t s);
@@ -316,6 +326,11 @@ void launch_mt_adam(const MTEntry* tab, const int2* chunks, int nchunks, AdamHyp
 // the two norm launches are skipped and every ratio is 1.
 void launch_mt_lars(const MTEntry* tab, const int2* chunks, int nchunks, const int2* spans, int ntensors,
                     float2* partials, float* trust, float eta, float eps, LarsHyper h, hipStream_t s);
+// LAMB step.  trust != null: moments + per-chunk (sum w^2, sum u^2) into partials [nchunks], per-tensor
+// trust ratios |w| / |u| into trust [ntensors], then the update.  trust == null (a non-adaptive group):
+// one launch, the moments kernel applies the update itself with every ratio 1.
+void launch_mt_lamb(const MTEntry* tab, const int2* chunks, int nchunks, const int2* spans, int ntensors,
+                    float2* partials, float* trust, LambHyper h, hipStream_t s);
 void launch_cdr_threshold(const MTEntry* tab, const int2* chunks, int nchunks, uint32_t* state, uint32_t* hist,
                           hipStream_t s);
 void launch_cdr_mask(const MTEntry* tab, const int2* chunks, int nchunks, const uint32_t* state, float clip,

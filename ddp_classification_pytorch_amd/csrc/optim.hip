@@ -12,6 +12,9 @@
 // * LARS over the same tables: per-chunk sums of squares, a per-tensor trust ratio, the SGD update on
 //   the scaled gradient; the learning rate optionally from a device scalar (HIP-graph replay under
 //   a per-iteration schedule).
+// * LAMB over the same tables and scratch: Adam's moments with the per-chunk sums of w^2 and u^2, the
+//   per-tensor trust ratio |w| / |u|, the update on the recomputed u.  Adam reads its learning rate
+//   from a device scalar too when one is given.
 // * CDR (CDR/main.py:186-204): threshold = k-th largest |g*w| over all 2-D/4-D
 //   parameters, found by a 4-pass 8-bit radix select over the float bit
 //   patterns (non-negative floats order like their uint32 bits) without
@@ -151,11 +154,8 @@ __global__ void __launch_bounds__(256) mt_norm2_kernel(const MTEntry* __restrict
 // One workgroup per tensor: its chunk partials summed in fp64 in a fixed order (thread t takes
 // partials t, t + 256, ... serially, then a shared-memory tree), so the merge adds no rounding of
 // its own; |w| and |grad_scale| |g| are rounded to fp32 once and the ratio is formed in fp32.
-__global__ void __launch_bounds__(256) lars_trust_kernel(const int2* __restrict__ spans, const float2* __restrict__ partials,
-                                                         float grad_scale, float wd, float eta, float eps,
-                                                         float* __restrict__ trust) {
-  __shared__ double sh[2][256];
-  const int2 sp = spans[blockIdx.x];  // (first chunk, number of chunks)
+// The fixed-order fp64 merge of one tensor's chunk partials (256 threads); the sums end in sh[.][0].
+__device__ __forceinline__ void merge_partials(const int2 sp, const float2* __restrict__ partials, double (*sh)[256]) {
   double aw = 0.0, ag = 0.0;
   for (int c = threadIdx.x; c < sp.y; c += 256) {
     const float2 v = partials[sp.x + c];
@@ -172,6 +172,13 @@ __global__ void __launch_bounds__(256) lars_trust_kernel(const int2* __restrict_
     }
     __syncthreads();
   }
+}
+
+__global__ void __launch_bounds__(256) lars_trust_kernel(const int2* __restrict__ spans, const float2* __restrict__ partials,
+                                                         float grad_scale, float wd, float eta, float eps,
+                                                         float* __restrict__ trust) {
+  __shared__ double sh[2][256];
+  merge_partials(spans[blockIdx.x], partials, sh);  // spans: (first chunk, number of chunks)
   if (threadIdx.x == 0) {
     const float wn = (float)sqrt(sh[0][0]);
     const float gn = (float)(fabs((double)grad_scale) * sqrt(sh[1][0]));
@@ -255,12 +262,13 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(const MTEntry* __restrict_
     bc2 = -expm1f(t * h.lb2);
   }
   const float rbc2 = 1.f / sqrtf(bc2);
+  const float lr = h.lr_dev ? *h.lr_dev : h.lr;  // the device scalar: a replayed graph follows a schedule
   for (int64_t i = base + threadIdx.x; i < end; i += blockDim.x) {
     float g = e.g[i] * h.grad_scale;
     float p = e.p[i];
     if (h.wd != 0.f) {
       if (h.decoupled)
-        p *= 1.f - h.lr * h.wd;
+        p *= 1.f - lr * h.wd;
       else
         g += h.wd * p;
     }
@@ -269,7 +277,192 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(const MTEntry* __restrict_
     e.s1[i] = m;
     e.s2[i] = v;
     const float denom = sqrtf(v) * rbc2 + h.eps;
-    p -= (h.lr / bc1) * m / denom;
+    p -= (lr / bc1) * m / denom;
+    e.p[i] = p;
+    if (e.shadow) e.shadow[i] = f2bf(p);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// LAMB (You et al. 2020): Adam's moments, a layer-wise trust ratio in front of the update.
+//   g~ = grad_scale g;  m = b1 m + (1 - b1) g~;  v = b2 v + (1 - b2) g~^2
+//   r = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps);  u = r + wd w
+//   trust = |w| / |u|  (1 when not adaptive or a norm is 0);  w -= lr trust u
+// Adaptive: mt_lamb_moments (m, v, per-chunk (sum w^2, sum u^2)), lamb_trust, mt_lamb_update, which
+// recomputes u from w and the new m, v (40 B / element; u is never stored).  Not adaptive: the moments
+// kernel applies the update itself.  Both kernels form u with lamb_u, so the norm is taken over exactly
+// the u that is applied; no float atomics, every reduction in a fixed order.
+// ---------------------------------------------------------------------------
+
+// Bias corrections of this launch: (bc1, 1 / sqrt(bc2)); from the device step count when there is one.
+__device__ __forceinline__ void lamb_bias(const LambHyper& h, float& bc1, float& rbc2) {
+  float bc2 = h.bc2;
+  bc1 = h.bc1;
+  if (h.bias_correction && h.step_dev) {
+    const float t = (float)*h.step_dev;
+    bc1 = -expm1f(t * h.lb1);
+    bc2 = -expm1f(t * h.lb2);
+  }
+  rbc2 = 1.f / sqrtf(bc2);
+}
+
+// One element's moments and its u.  Every operation is named (no bare a * b + c for the compiler to
+// contract one way in the 16-byte loop and another in the 4-byte loop): both loops, and both
+// kernels, round alike.
+__device__ __forceinline__ void lamb_moments(float gin, float& m, float& v, const LambHyper& h) {
+  const float g = __fmul_rn(gin, h.grad_scale);
+  m = fmaf(h.beta1, m, __fmul_rn(h.omb1, g));
+  v = fmaf(h.beta2, v, __fmul_rn(h.omb2, __fmul_rn(g, g)));
+}
+
+__device__ __forceinline__ float lamb_u(float m, float v, float p, float bc1, float rbc2, const LambHyper& h) {
+  const float denom = fmaf(__fsqrt_rn(v), rbc2, h.eps);
+  const float r = __fdiv_rn(__fdiv_rn(m, bc1), denom);
+  return h.wd != 0.f ? fmaf(h.wd, p, r) : r;
+}
+
+// One workgroup per chunk, thread-to-element ownership and accumulation order of mt_norm2_kernel:
+// thread t owns the chunk elements 4 (t + 256 k) + u.  APPLY (non-adaptive group): w = fma(-lr, u, w)
+// here, no partials.  Otherwise partials[blockIdx.x] = (sum w^2, sum u^2), w untouched.
+template <bool APPLY>
+__global__ void __launch_bounds__(256) mt_lamb_moments_kernel(const MTEntry* __restrict__ tab,
+                                                              const int2* __restrict__ chunks,
+                                                              float2* __restrict__ partials, LambHyper h) {
+  __shared__ float red[2][16];
+  const int2 ck = chunks[blockIdx.x];
+  const MTEntry e = tab[ck.x];
+  const int64_t base = (int64_t)ck.y * kChunk;
+  const int len = (int)(min(e.n, base + kChunk) - base);
+  float* p = e.p + base;
+  const float* g = e.g + base;
+  float* m = e.s1 + base;
+  float* v = e.s2 + base;
+  bf16* shadow = (APPLY && e.shadow) ? e.shadow + base : nullptr;
+  float bc1, rbc2;
+  lamb_bias(h, bc1, rbc2);
+  const float nlr = APPLY ? -(h.lr_dev ? *h.lr_dev : h.lr) : 0.f;
+  float sw = 0.f, su = 0.f;
+  const uintptr_t mis = ((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u;
+  const uintptr_t smis = shadow ? ((uintptr_t)shadow & 7u) : 0;
+  if (mis == 0 && smis == 0 && (len & 3) == 0) {
+    const int n4 = len >> 2;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int j = threadIdx.x + 256 * k;
+      if (j < n4) {
+        float pv[4], gv[4], mv[4], vv[4];
+        *(float4*)pv = ((const float4*)p)[j];
+        *(float4*)gv = ((const float4*)g)[j];
+        *(float4*)mv = ((const float4*)m)[j];
+        *(float4*)vv = ((const float4*)v)[j];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          lamb_moments(gv[u], mv[u], vv[u], h);
+          const float uu = lamb_u(mv[u], vv[u], pv[u], bc1, rbc2, h);
+          if (APPLY) {
+            pv[u] = fmaf(nlr, uu, pv[u]);
+          } else {
+            sw = fmaf(pv[u], pv[u], sw);
+            su = fmaf(uu, uu, su);
+          }
+        }
+        ((float4*)m)[j] = *(float4*)mv;
+        ((float4*)v)[j] = *(float4*)vv;
+        if (APPLY) {
+          ((float4*)p)[j] = *(float4*)pv;
+          if (shadow) {
+            bf16x4 sv;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) sv[u] = f2bf(pv[u]);
+            *(bf16x4*)(shadow + 4 * j) = sv;
+          }
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i0 = 4 * (threadIdx.x + 256 * k);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int i = i0 + u;
+        if (i < len) {
+          float pv = p[i], mv = m[i], vv = v[i];
+          lamb_moments(g[i], mv, vv, h);
+          const float uu = lamb_u(mv, vv, pv, bc1, rbc2, h);
+          m[i] = mv;
+          v[i] = vv;
+          if (APPLY) {
+            pv = fmaf(nlr, uu, pv);
+            p[i] = pv;
+            if (shadow) shadow[i] = f2bf(pv);
+          } else {
+            sw = fmaf(pv, pv, sw);
+            su = fmaf(uu, uu, su);
+          }
+        }
+      }
+    }
+  }
+  if (!APPLY) {
+    sw = block_sum(sw, red[0]);
+    su = block_sum(su, red[1]);
+    if (threadIdx.x == 0) partials[blockIdx.x] = make_float2(sw, su);
+  }
+}
+
+// One workgroup per tensor: lars_trust_kernel's merge; |w| and |u| rounded to fp32 once each, the
+// ratio formed in fp32.
+__global__ void __launch_bounds__(256) lamb_trust_kernel(const int2* __restrict__ spans, const float2* __restrict__ partials,
+                                                         float* __restrict__ trust) {
+  __shared__ double sh[2][256];
+  merge_partials(spans[blockIdx.x], partials, sh);
+  if (threadIdx.x == 0) {
+    const float wn = (float)sqrt(sh[0][0]);
+    const float un = (float)sqrt(sh[1][0]);
+    trust[blockIdx.x] = (wn > 0.f && un > 0.f) ? __fdiv_rn(wn, un) : 1.f;
+  }
+}
+
+// w = fma(-(lr trust), u, w), u recomputed from w and the moments mt_lamb_moments left; the learning
+// rate from the device scalar when one is given.
+__global__ void __launch_bounds__(256) mt_lamb_update_kernel(const MTEntry* __restrict__ tab,
+                                                             const int2* __restrict__ chunks, LambHyper h) {
+  const int2 ck = chunks[blockIdx.x];
+  const MTEntry e = tab[ck.x];
+  const int64_t base = (int64_t)ck.y * kChunk;
+  const int64_t end = min(e.n, base + kChunk);
+  float bc1, rbc2;
+  lamb_bias(h, bc1, rbc2);
+  const float nlt = -__fmul_rn(h.lr_dev ? *h.lr_dev : h.lr, h.trust[ck.x]);
+  const uintptr_t mis = ((uintptr_t)(e.p + base) | (uintptr_t)(e.s1 + base) | (uintptr_t)(e.s2 + base)) & 15u;
+  const uintptr_t smis = e.shadow ? ((uintptr_t)(e.shadow + base) & 7u) : 0;
+  if (mis == 0 && smis == 0 && ((end - base) & 3) == 0) {
+    const int64_t n4 = (end - base) >> 2;
+    float4* p4 = (float4*)(e.p + base);
+    const float4* m4 = (const float4*)(e.s1 + base);
+    const float4* v4 = (const float4*)(e.s2 + base);
+#pragma unroll 4
+    for (int64_t j = threadIdx.x; j < n4; j += blockDim.x) {
+      float pv[4], mv[4], vv[4];
+      *(float4*)pv = p4[j];
+      *(float4*)mv = m4[j];
+      *(float4*)vv = v4[j];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) pv[u] = fmaf(nlt, lamb_u(mv[u], vv[u], pv[u], bc1, rbc2, h), pv[u]);
+      p4[j] = *(float4*)pv;
+      if (e.shadow) {
+        bf16x4 sv;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sv[u] = f2bf(pv[u]);
+        *(bf16x4*)(e.shadow + base + 4 * j) = sv;
+      }
+    }
+    return;
+  }
+  for (int64_t i = base + threadIdx.x; i < end; i += blockDim.x) {
+    float p = e.p[i];
+    p = fmaf(nlt, lamb_u(e.s1[i], e.s2[i], p, bc1, rbc2, h), p);
     e.p[i] = p;
     if (e.shadow) e.shadow[i] = f2bf(p);
   }
@@ -383,6 +576,18 @@ void launch_mt_lars(const MTEntry* tab, const int2* chunks, int nchunks, const i
 }
 void launch_mt_adam(const MTEntry* tab, const int2* chunks, int nchunks, AdamHyper h, hipStream_t s) {
   if (nchunks) hipLaunchKernelGGL(mt_adam_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, h);
+}
+void launch_mt_lamb(const MTEntry* tab, const int2* chunks, int nchunks, const int2* spans, int ntensors,
+                    float2* partials, float* trust, LambHyper h, hipStream_t s) {
+  if (!nchunks) return;
+  h.trust = trust;
+  if (!trust) {  // not adaptive: one launch, every ratio 1
+    hipLaunchKernelGGL((mt_lamb_moments_kernel<true>), dim3(nchunks), dim3(256), 0, s, tab, chunks, partials, h);
+    return;
+  }
+  hipLaunchKernelGGL((mt_lamb_moments_kernel<false>), dim3(nchunks), dim3(256), 0, s, tab, chunks, partials, h);
+  hipLaunchKernelGGL(lamb_trust_kernel, dim3(ntensors), dim3(256), 0, s, spans, partials, trust);
+  hipLaunchKernelGGL(mt_lamb_update_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, h);
 }
 void launch_cdr_threshold(const MTEntry* tab, const int2* chunks, int nchunks, uint32_t* state, uint32_t* hist,
                           hipStream_t s) {

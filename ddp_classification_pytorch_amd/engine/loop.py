@@ -18,8 +18,9 @@ Differences from the reference, all deliberate:
   wired here for every workload that goes through this loop);
 * ``--lr-decay poly`` decays the learning rate per iteration after the warm-up (PolyDecay, a pure
   function of the global step) in place of the per-epoch scheduler; an optimizer with a device
-  learning rate (FusedLARS: ``push_lr``) replays one captured HIP graph through warm-up and decay,
-  every other optimizer runs such steps eagerly as before;
+  learning rate (``optimizer.device_lr``: FusedLARS, FusedLAMB, and FusedSGD / FusedAdam under
+  ``--device-lr``) replays one captured HIP graph through warm-up, decay and epoch boundaries,
+  every other optimizer runs such steps eagerly and recaptures as before;
 * GPU step time from HIP events (``gpu_ms_per_step`` in the JSONL log, no host
   sync beyond the log interval's), a per-rank heartbeat file
   (``heartbeat_rank<r>.txt``: wall time, step, loss every ``--heartbeat-every``
@@ -90,7 +91,8 @@ class ClassificationLoop:
         if self._poly_on:
             self.scheduler = None  # the per-iteration decay replaces the epoch scheduler for this run
         # the optimizer's kernels read the learning rate from the device: a captured step follows it
-        self._dev_lr = hasattr(optimizer, "push_lr")
+        # (the per-instance switch, not the method: every fused optimizer has push_lr)
+        self._dev_lr = bool(getattr(optimizer, "device_lr", False))
 
     # ------------------------------------------------------------------ persistence
     def _ckpt(self, name):
@@ -140,7 +142,7 @@ class ClassificationLoop:
         """--graph: single-process GPU runs replay the whole step as a HIP graph (engine/graph.py),
         recaptured at every epoch start (the learning rate is a captured kernel argument) and
         after the LR warm-up (its steps run eagerly: the LR changes every iteration).  An optimizer
-        with a device learning rate (``push_lr``) keeps one capture through all of that."""
+        with a device learning rate (``device_lr``) keeps one capture through all of that."""
         a = self.args
         self._grapher = None
         graph_safe = not any(isinstance(m, torch.nn.parallel.DistributedDataParallel) for m in self.train_modules)

@@ -1,29 +1,47 @@
-from .fused import FusedAdam, FusedLARS, FusedSGD
+from .fused import FusedAdam, FusedLAMB, FusedLARS, FusedSGD
 from .schedulers import LinearWarmup, MultiStepLR, PolyDecay, StepLR
+
+
+def _split_1d(params, keep_1d):
+    """The usual large-batch recipe: BN scales / shifts and biases (ndim <= 1) step without the
+    layer-wise rate and without weight decay; every weight tensor gets both."""
+    params = list(params)
+    if keep_1d:
+        return [dict(params=params)]
+    groups = [dict(params=[p for p in params if p.ndim >= 2]),
+              dict(params=[p for p in params if p.ndim <= 1], adapt=False, weight_decay=0.0)]
+    return [g for g in groups if g["params"]]
 
 
 def build_optimizer(name: str, params, lr: float, momentum: float = 0.9, weight_decay: float = 0.0,
                     nesterov: bool = False, betas=(0.9, 0.999), lars_eta: float = 1e-3, lars_eps: float = 1e-8,
-                    lars_keep_1d: bool = False):
+                    lars_keep_1d: bool = False, lamb_eps: float = 1e-6, lamb_bias_correction: bool = True,
+                    lamb_keep_1d: bool = False, device_lr: bool = False):
+    """``device_lr``: FusedSGD / FusedAdam read the learning rate from the device (FusedLARS and
+    FusedLAMB always do)."""
     name = name.lower()
     if name == "sgd":
-        return FusedSGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov)
+        return FusedSGD(params, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
+                        device_lr=device_lr)
     if name in ("adam", "adamw"):
-        return FusedAdam(params, lr=lr, betas=betas, weight_decay=weight_decay, decoupled=name == "adamw")
+        return FusedAdam(params, lr=lr, betas=betas, weight_decay=weight_decay, decoupled=name == "adamw",
+                         device_lr=device_lr)
     if name == "lars":
-        # the usual large-batch recipe: BN scales / shifts and biases (ndim <= 1) take plain momentum
-        # SGD without weight decay; every weight tensor gets the layer-wise rate and the decay
-        params = list(params)
-        if lars_keep_1d:
-            groups = [dict(params=params)]
-        else:
-            groups = [dict(params=[p for p in params if p.ndim >= 2]),
-                      dict(params=[p for p in params if p.ndim <= 1], adapt=False, weight_decay=0.0)]
-            groups = [g for g in groups if g["params"]]
-        return FusedLARS(groups, lr=lr, momentum=momentum, weight_decay=weight_decay, nesterov=nesterov,
-                         eta=lars_eta, eps=lars_eps)
+        return FusedLARS(_split_1d(params, lars_keep_1d), lr=lr, momentum=momentum, weight_decay=weight_decay,
+                         nesterov=nesterov, eta=lars_eta, eps=lars_eps)
+    if name == "lamb":
+        return FusedLAMB(_split_1d(params, lamb_keep_1d), lr=lr, betas=betas, weight_decay=weight_decay,
+                         eps=lamb_eps, bias_correction=lamb_bias_correction)
     raise ValueError(f"unknown optimizer {name}")
 
 
-__all__ = ["FusedSGD", "FusedAdam", "FusedLARS", "LinearWarmup", "MultiStepLR", "PolyDecay", "StepLR",
-           "build_optimizer"]
+def optimizer_flags(args):
+    """build_optimizer's keyword arguments from the command line (config.py)."""
+    return dict(lars_eta=getattr(args, "lars_eta", 1e-3), lars_eps=getattr(args, "lars_eps", 1e-8),
+                lars_keep_1d=getattr(args, "lars_keep_1d", False), lamb_eps=getattr(args, "lamb_eps", 1e-6),
+                lamb_bias_correction=getattr(args, "lamb_bias_correction", True),
+                lamb_keep_1d=getattr(args, "lamb_keep_1d", False), device_lr=getattr(args, "device_lr", False))
+
+
+__all__ = ["FusedSGD", "FusedAdam", "FusedLARS", "FusedLAMB", "LinearWarmup", "MultiStepLR", "PolyDecay", "StepLR",
+           "build_optimizer", "optimizer_flags"]

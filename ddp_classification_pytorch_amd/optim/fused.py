@@ -17,11 +17,13 @@ counter that the captured step itself increments (``mt_adam(step_dev=...)``), an
 :meth:`FusedAdam.on_graph_replay` advances the host ``state["step"]`` mirrors so
 ``state_dict`` / resume see the true count.  SGD has no step-dependent argument; the
 learning rate of a captured step is the one at capture (the grapher recaptures when it
-changes).
+changes) unless the optimizer was built with ``device_lr=True``: the kernels then read the
+rate from a device scalar that :meth:`push_lr` keeps current, and one capture follows a
+per-iteration schedule.
 
 :class:`FusedLARS` (layer-wise adaptive rate scaling for large global batches) adds a per-tensor
-trust ratio in front of the SGD update (``mt_lars``) and reads its learning rate from a device
-scalar, so a captured step follows a per-iteration schedule without recapture.
+trust ratio in front of the SGD update (``mt_lars``), :class:`FusedLAMB` one in front of Adam's
+(``mt_lamb``); both always read their learning rate from the device.
 """
 from __future__ import annotations
 
@@ -65,9 +67,52 @@ class _TableCache:
         return self.table, self.chunks
 
 
-class FusedSGD(torch.optim.Optimizer):
+def _capturing():
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+class _DeviceLR:
+    """The device learning rate of the fused optimizers.  With ``self.device_lr`` each group owns a
+    ``float32[1]`` device tensor that the update kernel reads.  ``group["lr"]`` stays the host truth
+    (schedulers, checkpoints, logging); :meth:`push_lr` writes it to the device when it changed.  A
+    HIP-graph replay therefore follows a per-iteration schedule without recapture: change
+    ``group["lr"]``, call ``push_lr()``, replay.  The training loop decides on the per-instance
+    ``device_lr`` attribute (always true on FusedLARS / FusedLAMB, opt-in on FusedSGD / FusedAdam)."""
+
+    device_lr = False
+
+    def _init_device_lr(self, device_lr):
+        self.device_lr = bool(device_lr)
+        self._lr_dev = {}        # group index -> [float32[1] device tensor, host value last written]
+
+    def push_lr(self):
+        """Write each group's ``lr`` into its device scalar on the current stream if the host value
+        changed since the last write; a no-op otherwise (and before the first GPU step, which creates
+        the scalars from the learning rates of that moment, and without ``device_lr``)."""
+        for gi, ent in self._lr_dev.items():
+            lr = float(self.param_groups[gi]["lr"])
+            if ent[1] != lr:
+                ent[0].fill_(lr)
+                ent[1] = lr
+
+    def _lr_tensor(self, gi, group, device):
+        ent = self._lr_dev.get(gi)
+        if ent is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{type(self).__name__}: the device learning rate must be created by an eager "
+                                   "step before capture")
+            lr = float(group["lr"])
+            ent = self._lr_dev[gi] = [torch.full((1,), lr, dtype=torch.float32, device=device), lr]
+        return ent[0]
+
+    def _forget_pushed_lr(self):
+        for ent in self._lr_dev.values():
+            ent[1] = None  # the (loaded) learning rates are written at the next push
+
+
+class FusedSGD(_DeviceLR, torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 grad_scale=1.0):
+                 grad_scale=1.0, device_lr=False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
@@ -77,6 +122,7 @@ class FusedSGD(torch.optim.Optimizer):
         self._fast = {}          # launch key -> (pointer fingerprint, table, chunks): see _update
         self._gid = None         # id(param) -> group index (step_params), rebuilt when groups change
         self._reducer_stepped = False
+        self._init_device_lr(device_lr)
 
     def mark_stepped_by_reducer(self):
         """The bucket engine (parallel/reducer.py) already applied this step per bucket: the next
@@ -87,6 +133,7 @@ class FusedSGD(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._fast.clear()  # new momentum buffers: the cached tables point at the old ones
+        self._forget_pushed_lr()
 
     def _group_index(self):
         sig = tuple(len(g["params"]) for g in self.param_groups)
@@ -103,6 +150,8 @@ class FusedSGD(torch.optim.Optimizer):
         if self._reducer_stepped:
             self._reducer_stepped = False
             return loss
+        if self.device_lr and not _capturing():
+            self.push_lr()
         self._step_subset(None)
         Fn.bump_weight_generation()
         return loss
@@ -113,6 +162,8 @@ class FusedSGD(torch.optim.Optimizer):
         hyper-parameters apply to its own members.  The caller bumps the weight generation.
         Host cost is O(len(params)): the bucket's members are grouped by a cached param -> group
         map instead of scanning every group (the bucket engine calls this once per bucket)."""
+        if self.device_lr and not _capturing():
+            self.push_lr()
         gid = self._group_index()
         by_group = {}
         for p in params:
@@ -154,8 +205,7 @@ class FusedSGD(torch.optim.Optimizer):
             fp = tuple((p.data_ptr(), p.grad.data_ptr()) for p in params)
             hit = self._fast.get(key) if not first else None
             if hit is not None and hit[0] == fp:
-                _ext.hip_ops().mt_sgd(hit[1], hit[2], group["lr"], mom, group["dampening"], group["weight_decay"],
-                                      group["nesterov"], first, group["grad_scale"])
+                self._launch(gi, group, hit[1], hit[2], first)
                 return
             entries = []
             for p in params:
@@ -170,8 +220,7 @@ class FusedSGD(torch.optim.Optimizer):
             table, chunks = self._tables.setdefault(key, _TableCache()).get(entries, params[0].device)
             if not first:
                 self._fast[key] = (fp, table, chunks)
-            _ext.hip_ops().mt_sgd(table, chunks, group["lr"], mom, group["dampening"], group["weight_decay"],
-                                  group["nesterov"], first, group["grad_scale"])
+            self._launch(gi, group, table, chunks, first)
             return
         for p in params:
             g = p.grad * group["grad_scale"]
@@ -186,19 +235,33 @@ class FusedSGD(torch.optim.Optimizer):
                 g = g + mom * buf if group["nesterov"] else buf
             p.add_(g, alpha=-group["lr"])
 
+    def _launch(self, gi, group, table, chunks, first):
+        if self.device_lr:
+            # mt_lars without a trust table is the mt_sgd step, bit for bit, with the rate read from the device
+            _ext.hip_ops().mt_lars(table, chunks, None, None, None, group["lr"], group["momentum"], group["dampening"],
+                                   group["weight_decay"], group["nesterov"], first, group["grad_scale"], 0.0, 0.0,
+                                   self._lr_tensor(gi, group, table.device))
+            return
+        _ext.hip_ops().mt_sgd(table, chunks, group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
+                              group["nesterov"], first, group["grad_scale"])
 
-class FusedAdam(torch.optim.Optimizer):
+
+class FusedAdam(_DeviceLR, torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
-                 grad_scale=1.0):
+                 grad_scale=1.0, device_lr=False):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=decoupled,
                         grad_scale=grad_scale)
         super().__init__(params, defaults)
+        self._init_runtime(device_lr)
+
+    def _init_runtime(self, device_lr):
         self._tables = {}
         self._dsteps = {}        # launch key -> [device int32 step, host mirror, params]
         self._captured = None    # launch keys of the step being / last captured into a HIP graph
         self._reducer_stepped = False
         self._bucket_capture_open = False
         self._gid = None
+        self._init_device_lr(device_lr)
 
     def mark_stepped_by_reducer(self):
         self._reducer_stepped = True
@@ -219,6 +282,7 @@ class FusedAdam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._dsteps.clear()  # re-seeded from the loaded host step counts at the next step
+        self._forget_pushed_lr()
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -229,9 +293,11 @@ class FusedAdam(torch.optim.Optimizer):
         if self._reducer_stepped:
             self._reducer_stepped = False
             return loss
-        capturing = torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+        capturing = _capturing()
         if capturing:
             self._captured = []
+        elif self.device_lr:
+            self.push_lr()
         self._step_subset(None)
         Fn.bump_weight_generation()
         return loss
@@ -239,9 +305,12 @@ class FusedAdam(torch.optim.Optimizer):
     @torch.no_grad()
     def step_params(self, params):
         """Update only ``params`` (one bucket of the bucket engine); see FusedSGD.step_params."""
-        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing() and not self._bucket_capture_open:
+        capturing = _capturing()
+        if capturing and not self._bucket_capture_open:
             self._captured = []  # the first bucket of a captured backward: this capture's launch keys
             self._bucket_capture_open = True
+        if self.device_lr and not capturing:
+            self.push_lr()
         gid = FusedSGD._group_index(self)
         by_group = {}
         for p in params:
@@ -272,6 +341,21 @@ class FusedAdam(torch.optim.Optimizer):
         for step, sub in sorted(by_step.items()):
             self._update(gi, group, sub, step)
 
+    def _device_step(self, key, step, params):
+        """The launch's device step counter, advanced to ``step`` on the current stream."""
+        ds = self._dsteps.get(key)
+        if ds is None or ds[1] != step - 1:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{type(self).__name__}: step counters must be seeded by an eager step before "
+                                   "capture")
+            ds = self._dsteps[key] = [torch.full((1,), step - 1, dtype=torch.int32, device=params[0].device),
+                                      step - 1, params]
+        ds[0].add_(1)  # captured with the step: every replay advances the device count
+        ds[1], ds[2] = step, params
+        if self._captured is not None and torch.cuda.is_current_stream_capturing():
+            self._captured.append(key)
+        return ds[0]
+
     def _update(self, gi, group, params, step):
         b1, b2 = group["betas"]
         if params[0].is_cuda:
@@ -280,20 +364,12 @@ class FusedAdam(torch.optim.Optimizer):
                 st = self.state[p]
                 entries.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
                                 st["exp_avg_sq"].data_ptr(), 0, p.numel()))
+            dev = params[0].device
             key = (gi, len(params), params[0].data_ptr())
-            table, chunks = self._tables.setdefault(key, _TableCache()).get(entries, params[0].device)
-            ds = self._dsteps.get(key)
-            if ds is None or ds[1] != step - 1:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("FusedAdam: step counters must be seeded by an eager step before capture")
-                ds = self._dsteps[key] = [torch.full((1,), step - 1, dtype=torch.int32, device=params[0].device),
-                                          step - 1, params]
-            ds[0].add_(1)  # captured with the step: every replay advances the device count
-            ds[1], ds[2] = step, params
-            if self._captured is not None and torch.cuda.is_current_stream_capturing():
-                self._captured.append(key)
+            table, chunks = self._tables.setdefault(key, _TableCache()).get(entries, dev)
             _ext.hip_ops().mt_adam(table, chunks, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
-                                   group["decoupled"], group["grad_scale"], ds[0])
+                                   group["decoupled"], group["grad_scale"], self._device_step(key, step, params),
+                                   self._lr_tensor(gi, group, dev) if self.device_lr else None)
             return
         bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
         for p in params:
@@ -366,57 +442,23 @@ class FusedLARS(FusedSGD):
         self._fast = {}          # launch key -> (pointer fingerprint, _LarsTables)
         self._gid = None
         self._reducer_stepped = False
-        self._lr_dev = {}        # group index -> [float32[1] device tensor, host value last written]
+        self._init_device_lr(True)   # push_lr / _lr_tensor: see _DeviceLR
         self._trust = {}         # id(param) -> (trust tensor, index) of its last step
         self._ones = {}          # device -> float32[1] of 1.0 (trust_of for non-adaptive groups)
         self._via = "step"       # which entry point is stepping: part of the launch key
-
-    # ------------------------------------------------------------------ device learning rate
-    def push_lr(self):
-        """Write each group's ``lr`` into its device scalar on the current stream if the host value
-        changed since the last write; a no-op otherwise (and before the first GPU step, which creates
-        the scalars from the learning rates of that moment)."""
-        for gi, ent in self._lr_dev.items():
-            lr = float(self.param_groups[gi]["lr"])
-            if ent[1] != lr:
-                ent[0].fill_(lr)
-                ent[1] = lr
-
-    def _lr_tensor(self, gi, group, device):
-        ent = self._lr_dev.get(gi)
-        if ent is None:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError("FusedLARS: the device learning rate must be created by an eager step before "
-                                   "capture")
-            lr = float(group["lr"])
-            ent = self._lr_dev[gi] = [torch.full((1,), lr, dtype=torch.float32, device=device), lr]
-        return ent[0]
 
     def trust_of(self, p):
         """The trust ratio of ``p``'s last step as a device scalar view (no sync); 1 for a parameter
         of a non-adaptive group, None before its first step."""
         return self._trust.get(id(p))
 
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        for ent in self._lr_dev.values():
-            ent[1] = None  # the loaded learning rates are written at the next push
-
-    @staticmethod
-    def _capturing():
-        return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
-
     @torch.no_grad()
     def step(self, closure=None):
-        if not self._capturing():
-            self.push_lr()
         self._via = "step"
         return super().step(closure)
 
     @torch.no_grad()
     def step_params(self, params):
-        if not self._capturing():
-            self.push_lr()
         self._via = "bucket"
         super().step_params(params)
 
@@ -479,3 +521,100 @@ class FusedLARS(FusedSGD):
                     buf.mul_(mom).add_(g, alpha=1 - group["dampening"])
                 g = g + mom * buf if group["nesterov"] else buf
             p.add_(g, alpha=-group["lr"])
+
+
+class FusedLAMB(FusedAdam):
+    """LAMB (You et al. 2020): Adam's moments with a layer-wise trust ratio in front of the update.
+    Per tensor, ``t`` being that parameter's step count as in FusedAdam:
+
+        g~ = grad_scale * g
+        m  = b1 m + (1 - b1) g~            v = b2 v + (1 - b2) g~^2
+        r  = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps)     bc_i = 1 - b_i^t, or 1 with bias_correction=False
+        u  = r + wd * w
+        trust = |w| / |u|   if adapt and |w| > 0 and |u| > 0, else 1
+        w -= lr * trust * u
+
+    GPU: an adaptive launch of the ``mt_lamb`` op is three kernels (moments + per-chunk sums of w^2 and
+    u^2, per-tensor trust ratios merged in fp64 in a fixed order, the update on the recomputed u); a
+    non-adaptive group takes one.  No float atomics: a step is bit-reproducible.  The learning rate is
+    always read from the device (see :class:`_DeviceLR`), the bias corrections from FusedAdam's device
+    step counter: one captured HIP graph follows both.
+    """
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, grad_scale=1.0,
+                 bias_correction=True, adapt=True):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
+                        bias_correction=bias_correction, adapt=adapt)
+        torch.optim.Optimizer.__init__(self, params, defaults)
+        self._init_runtime(True)
+        self._trust = {}         # id(param) -> trust ratio (device scalar view) of its last step
+        self._trust_src = {}     # launch key -> what self._trust was last filled from
+        self._ones = {}          # device -> float32 scalar 1.0 (trust_of for non-adaptive groups)
+        self._via = "step"       # which entry point is stepping: part of the launch key
+
+    trust_of = FusedLARS.trust_of
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        self._via = "step"
+        return super().step(closure)
+
+    @torch.no_grad()
+    def step_params(self, params):
+        self._via = "bucket"
+        super().step_params(params)
+
+    def _update(self, gi, group, params, step):
+        b1, b2 = group["betas"]
+        wd, gs, eps = group["weight_decay"], group["grad_scale"], group["eps"]
+        adapt, bias = bool(group["adapt"]), bool(group["bias_correction"])
+        if params[0].is_cuda:
+            dev = params[0].device
+            entries = []
+            for p in params:
+                if not (p.is_contiguous() and p.grad.is_contiguous()):
+                    raise RuntimeError("FusedLAMB needs contiguous params and grads")
+                if p.dtype != torch.float32 or p.grad.dtype != torch.float32:
+                    raise RuntimeError("FusedLAMB expects fp32 master params and grads")
+                st = self.state[p]
+                entries.append((p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(),
+                                st["exp_avg_sq"].data_ptr(), 0, p.numel()))
+            # step() on the compute stream and step_params() on the comm stream never share scratch
+            key = (self._via, gi, len(params), params[0].data_ptr())
+            tabs = self._tables.setdefault(key, _LarsTables()).get(entries, dev)
+            src = (tabs.trust, adapt, tuple(id(p) for p in params))
+            old = self._trust_src.get(key)
+            if old is None or old[0] is not src[0] or old[1:] != src[1:]:
+                self._trust_src[key] = src
+                if adapt:
+                    for i, p in enumerate(params):
+                        self._trust[id(p)] = tabs.trust[i]
+                else:
+                    one = self._ones.get(dev)
+                    if one is None:
+                        one = self._ones[dev] = torch.ones((), dtype=torch.float32, device=dev)
+                    for p in params:
+                        self._trust[id(p)] = one
+            _ext.hip_ops().mt_lamb(tabs.table, tabs.chunks, tabs.spans if adapt else None,
+                                   tabs.partials if adapt else None, tabs.trust if adapt else None, group["lr"], b1, b2,
+                                   eps, wd, step, bias, gs, self._device_step(key, step, params),
+                                   self._lr_tensor(gi, group, dev))
+            return
+        # CPU: the same formulas in fp32 (norms merged in fp64, as the trust kernel does)
+        bc1, bc2 = (1 - b1 ** step, 1 - b2 ** step) if bias else (1.0, 1.0)
+        for p in params:
+            st = self.state[p]
+            g = p.grad * gs
+            st["exp_avg"].mul_(b1).add_(g, alpha=1 - b1)
+            st["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1 - b2)
+            u = (st["exp_avg"] / bc1) / (st["exp_avg_sq"].sqrt() / math.sqrt(bc2) + eps)
+            if wd:
+                u = u + wd * p
+            trust = torch.ones((), dtype=torch.float32)
+            if adapt:
+                wn = (p.detach() * p.detach()).sum(dtype=torch.float64).sqrt().float()
+                un = (u * u).sum(dtype=torch.float64).sqrt().float()
+                if wn > 0 and un > 0:
+                    trust = wn / un
+            self._trust[id(p)] = trust
+            p.add_(u, alpha=-float(torch.tensor(group["lr"], dtype=torch.float32) * trust))

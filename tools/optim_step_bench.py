@@ -1,16 +1,18 @@
-"""Step time of FusedLARS against FusedSGD over ResNet-50's parameter tensors (25.6M elements).
+"""Step time of the fused optimizers over ResNet-50's parameter tensors (25.6M elements): FusedLARS
+against FusedSGD, FusedLAMB against FusedAdam.
 
-    python tools/optim_step_bench.py [--steps 200] [--rounds 5] [--out FILE]
+    python tools/optim_step_bench.py [--steps 200] [--rounds 5] [--arms sgd,lars,adam,lamb] [--out FILE]
 
-Both optimizers step their own copies of the same parameters and gradients (momentum 0.9, weight
-decay 1e-4), eagerly and as a replayed HIP graph of one step.  Timing: HIP events around blocks of
-``--steps`` steps after a warm-up, the two arms alternating block by block; the figure per arm is
-the median over ``--rounds`` blocks, with the spread printed.
+Every optimizer steps its own copy of the same parameters and gradients (weight decay 1e-4; momentum
+0.9 for SGD / LARS), eagerly and as a replayed HIP graph of one step.  Timing: HIP events around
+blocks of ``--steps`` steps after a warm-up, the arms alternating block by block; the figure per arm
+is the median over ``--rounds`` blocks, with the spread printed.
 
-Byte accounting: the SGD step reads p, g, buf and writes p, buf (20 B / element); LARS reads p and g
-once more for the norms (28 B / element): 1.4x the traffic, plus the norm and trust launches.  The
-script prints the measured ratio and, beside it, each arm's bytes / time; it makes no statement on
-where the second read of p and g is served from.
+Byte accounting per element: the SGD step reads p, g, buf and writes p, buf (20 B); LARS reads p and g
+once more for the norms (28 B); Adam reads p, g, m, v and writes p, m, v (28 B); LAMB's moments pass
+reads p, g, m, v and writes m, v, its update reads p, m, v and writes p (40 B).  The script prints
+the measured ratios and, beside them, each arm's bytes / time; it makes no statement on where a
+second read is served from.
 """
 import argparse
 import os
@@ -23,7 +25,17 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from ddp_classification_pytorch_amd import _ext  # noqa: E402
 from ddp_classification_pytorch_amd.models import build_model  # noqa: E402
-from ddp_classification_pytorch_amd.optim import FusedLARS, FusedSGD  # noqa: E402
+from ddp_classification_pytorch_amd.optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD  # noqa: E402
+
+# one adaptive group over every tensor for LARS / LAMB: the full traffic (build_optimizer's default
+# split leaves the 1-D tensors, 0.2 % of the elements, non-adaptive)
+ARMS = {
+    "sgd": (FusedSGD, dict(lr=0.1, momentum=0.9, weight_decay=1e-4), 20),
+    "lars": (FusedLARS, dict(lr=0.1, momentum=0.9, weight_decay=1e-4, eta=1e-3), 28),
+    "adam": (FusedAdam, dict(lr=1e-3, weight_decay=1e-4), 28),
+    "lamb": (FusedLAMB, dict(lr=1e-3, weight_decay=1e-4), 40),
+}
+RATIOS = (("lars", "sgd"), ("lamb", "adam"), ("adam", "sgd"))
 
 
 def _arm(cls, shapes, dev, seed, **kw):
@@ -31,8 +43,7 @@ def _arm(cls, shapes, dev, seed, **kw):
     ps = [(0.05 * torch.randn(s, generator=gen)).to(dev).requires_grad_(True) for s in shapes]
     for p in ps:
         p.grad = (1e-3 * torch.randn(p.shape, generator=gen)).to(dev)
-    opt = cls(ps, lr=0.1, momentum=0.9, weight_decay=1e-4, **kw)
-    return ps, opt
+    return ps, cls(ps, **kw)
 
 
 def _time_block(fn, steps):
@@ -49,41 +60,44 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--arms", default="sgd,lars,adam,lamb")
+    ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("optim_step_bench needs the GPU: a step time is not measured on the CPU")
     _ext.hip_ops()
     dev = torch.device("cuda", 0)
+    names = [k for k in a.arms.split(",") if k]
     shapes = [tuple(p.shape) for p in build_model("resnet50", num_classes=1000).parameters()]
     n = sum(int(torch.Size(s).numel()) for s in shapes)
-    lines = [f"# optim_step_bench: {len(shapes)} tensors, {n} elements (ResNet-50), momentum 0.9, wd 1e-4, "
+    lines = [f"# optim_step_bench: {len(shapes)} tensors, {n} elements (ResNet-50), wd 1e-4, "
              f"{a.rounds} alternating blocks of {a.steps} steps, median [min .. max] us per step",
              f"# device: {torch.cuda.get_device_name(0)}"]
-    _, sgd = _arm(FusedSGD, shapes, dev, 1)
-    # one adaptive group over every tensor: the full 28 B / element (build_optimizer's default split
-    # leaves the 1-D tensors, 0.2 % of the elements, non-adaptive)
-    _, lars = _arm(FusedLARS, shapes, dev, 1, eta=1e-3)
-    arms = {"sgd": sgd.step, "lars": lars.step}
-    for f in arms.values():  # first=True launches, tables, the device learning rate
+    arms = {k: _arm(ARMS[k][0], shapes, dev, 1, **ARMS[k][1])[1].step for k in names}
+    for f in arms.values():  # first launches, tables, the device learning rate and step counters
         for _ in range(3):
             f()
     torch.cuda.synchronize()
-    graphs = {}
-    side = torch.cuda.Stream()
-    for name, f in arms.items():
-        g = torch.cuda.CUDAGraph()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            f()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        with torch.cuda.graph(g):
-            f()
-        graphs[name] = g.replay
-    bytes_per = {"sgd": 20 * n, "lars": 28 * n}
+    modes = {"eager": arms}
+    if "graph" in a.modes:
+        graphs = {}
+        side = torch.cuda.Stream()
+        for name, f in arms.items():
+            g = torch.cuda.CUDAGraph()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                f()
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            with torch.cuda.graph(g):
+                f()
+            graphs[name] = g.replay
+        modes["graph"] = graphs
+    bytes_per = {k: ARMS[k][2] * n for k in names}
     res = {}
-    for mode, fns in (("eager", arms), ("graph", graphs)):
+    for mode in [m for m in a.modes.split(",") if m in modes]:
+        fns = modes[mode]
         for f in fns.values():
             _time_block(f, a.steps)  # warm-up of this mode
         t = {k: [] for k in fns}
@@ -95,9 +109,12 @@ def main(argv=None):
             res[(mode, k)] = med
             lines.append(f"{mode:5s} {k:4s} {med:8.1f} us  [{min(t[k]):.1f} .. {max(t[k]):.1f}]   "
                          f"{bytes_per[k] / 1e6:.0f} MB accounted -> {bytes_per[k] / med / 1e6:.2f} TB/s")
-        ratio = res[(mode, "lars")] / res[(mode, "sgd")]
-        lines.append(f"{mode:5s} LARS / SGD step-time ratio {ratio:.3f}  (traffic model 1.40; extra "
-                     f"{res[(mode, 'lars')] - res[(mode, 'sgd')]:.1f} us per step)")
+        for num, den in RATIOS:
+            if num in fns and den in fns:
+                ratio = res[(mode, num)] / res[(mode, den)]
+                lines.append(f"{mode:5s} {num.upper()} / {den.upper()} step-time ratio {ratio:.3f}  (traffic model "
+                             f"{ARMS[num][2] / ARMS[den][2]:.2f}; extra {res[(mode, num)] - res[(mode, den)]:.1f} us "
+                             "per step)")
     text = "\n".join(lines)
     print(text)
     if a.out:
