@@ -113,6 +113,17 @@ def build_parser() -> argparse.ArgumentParser:
       help="SGD / Adam / AdamW: the kernels read the learning rate from a device scalar, so one captured HIP "
            "graph follows warm-up, --lr-decay poly and the epoch scheduler without recapture (LARS and LAMB "
            "always do)")
+    a("--clip-grad-norm", dest="clip_grad_norm", type=float, default=0.0,
+      help="clip the global gradient norm of the optimizer to this value (clip_grad_norm_'s formula, computed "
+           "on the device; 0: off)")
+    a("--skip-nonfinite", dest="skip_nonfinite", action="store_true",
+      help="a step whose global gradient norm is inf or NaN changes no weight and no optimizer state")
+    a("--lars-trust-clip", dest="lars_trust_clip", action="store_true",
+      help="LARS: LARC's clip mode, trust <- min(trust / lr, 1): the layer-wise rate never exceeds lr")
+    a("--lamb-phi-min", dest="lamb_phi_min", type=float, default=0.0,
+      help="LAMB: lower clamp of |w| in the trust ratio (the paper's phi)")
+    a("--lamb-phi-max", dest="lamb_phi_max", type=float, default=float("inf"),
+      help="LAMB: upper clamp of |w| in the trust ratio")
     a("--lr-decay", dest="lr_decay", default="none", choices=["none", "poly"],
       help="poly: after --warmup-iters, lr = target * (1 - (step - warm) / (total - warm))^2 per iteration, in "
            "place of the per-epoch scheduler")

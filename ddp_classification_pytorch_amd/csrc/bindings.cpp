@@ -2006,6 +2006,50 @@ void mt_copy(const Tensor& table, const Tensor& chunks, double scale, int64_t mo
                       cur_stream());
 }
 
+// the control block of gradient-norm clipping (float32[8] viewed as dcp::ClipCtl), or null
+static dcp::ClipCtl* clip_ctl_ptr(const c10::optional<Tensor>& clip, const char* op) {
+  if (!clip.has_value() || !clip->defined()) return nullptr;
+  CHECK_DEV((*clip));
+  TORCH_CHECK(clip->scalar_type() == at::kFloat && clip->is_contiguous() &&
+                  clip->numel() * sizeof(float) == sizeof(dcp::ClipCtl),
+              op, ": clip float32[8]");
+  return reinterpret_cast<dcp::ClipCtl*>(clip->data_ptr());
+}
+
+// Per-chunk sums of g^2 of the table's tensors into partials[slots[row] + chunk] (float32 [nslots, 2]:
+// the sum and the step's epoch stamp); slots int32 [n] = first slot of each table row.
+void mt_gnorm2(const Tensor& table, const Tensor& chunks, const Tensor& slots, const Tensor& partials,
+               const Tensor& clip) {
+  CHECK_DEV(table);
+  CHECK_DEV(chunks);
+  CHECK_DEV(slots);
+  CHECK_DEV(partials);
+  TORCH_CHECK(slots.scalar_type() == at::kInt && slots.is_contiguous() && slots.numel() == table.size(0),
+              "mt_gnorm2: slots int32 [n]");
+  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.is_contiguous() && partials.dim() == 2 &&
+                  partials.size(1) == 2 && partials.size(0) >= chunks.size(0),
+              "mt_gnorm2: partials float [nslots >= k, 2]");
+  dcp::launch_mt_gnorm2(reinterpret_cast<const dcp::MTEntry*>(table.data_ptr()),
+                        reinterpret_cast<const int2*>(chunks.data_ptr()), (int)chunks.size(0), slots.data_ptr<int>(),
+                        clip_ctl_ptr(clip, "mt_gnorm2"), reinterpret_cast<dcp::GnormPartial*>(partials.data_ptr()),
+                        cur_stream());
+}
+
+// All slots merged into the control block: norm, coefficient (max_norm > 0, else 1), skip flag.
+void gnorm_finish(const Tensor& partials, const Tensor& slot_gs, double max_norm, bool skip_nonfinite,
+                  const Tensor& clip) {
+  CHECK_DEV(partials);
+  CHECK_DEV(slot_gs);
+  TORCH_CHECK(partials.scalar_type() == at::kFloat && partials.is_contiguous() && partials.dim() == 2 &&
+                  partials.size(1) == 2,
+              "gnorm_finish: partials float [nslots, 2]");
+  TORCH_CHECK(slot_gs.scalar_type() == at::kFloat && slot_gs.is_contiguous() && slot_gs.numel() == partials.size(0),
+              "gnorm_finish: slot_gs float [nslots]");
+  dcp::launch_gnorm_finish(reinterpret_cast<const dcp::GnormPartial*>(partials.data_ptr()), (int)partials.size(0),
+                           slot_gs.data_ptr<float>(), (float)max_norm, skip_nonfinite ? 1 : 0,
+                           clip_ctl_ptr(clip, "gnorm_finish"), cur_stream());
+}
+
 void mt_sgd(const Tensor& table, const Tensor& chunks, double lr, double momentum, double dampening, double wd,
             bool nesterov, bool first, double grad_scale) {
   CHECK_DEV(table);
@@ -2024,10 +2068,12 @@ void mt_sgd(const Tensor& table, const Tensor& chunks, double lr, double momentu
 void mt_lars(const Tensor& table, const Tensor& chunks, const c10::optional<Tensor>& spans,
              const c10::optional<Tensor>& partials, const c10::optional<Tensor>& trust, double lr, double momentum,
              double dampening, double wd, bool nesterov, bool first, double grad_scale, double eta, double eps,
-             const c10::optional<Tensor>& lr_dev) {
+             const c10::optional<Tensor>& lr_dev, const c10::optional<Tensor>& clip, bool trust_clip) {
   CHECK_DEV(table);
   CHECK_DEV(chunks);
   dcp::LarsHyper h;
+  h.clip = clip_ctl_ptr(clip, "mt_lars");
+  h.trust_clip = trust_clip ? 1 : 0;
   h.sgd = dcp::SgdHyper{(float)lr, (float)momentum, (float)dampening, (float)wd, (float)grad_scale, nesterov ? 1 : 0,
                         first ? 1 : 0};
   h.trust = nullptr;
@@ -2066,10 +2112,11 @@ void mt_lars(const Tensor& table, const Tensor& chunks, const c10::optional<Tens
 // the kernel -- a HIP-graph replay then applies the current step's correction, not the captured one
 void mt_adam(const Tensor& table, const Tensor& chunks, double lr, double beta1, double beta2, double eps, double wd,
              int64_t step, bool decoupled, double grad_scale, const c10::optional<Tensor>& step_dev,
-             const c10::optional<Tensor>& lr_dev) {
+             const c10::optional<Tensor>& lr_dev, const c10::optional<Tensor>& clip) {
   CHECK_DEV(table);
   CHECK_DEV(chunks);
   dcp::AdamHyper h;
+  h.clip = clip_ctl_ptr(clip, "mt_adam");
   h.step_dev = nullptr;
   h.lr_dev = nullptr;
   if (lr_dev.has_value() && lr_dev->defined()) {
@@ -2104,10 +2151,14 @@ void mt_adam(const Tensor& table, const Tensor& chunks, double lr, double beta1,
 void mt_lamb(const Tensor& table, const Tensor& chunks, const c10::optional<Tensor>& spans,
              const c10::optional<Tensor>& partials, const c10::optional<Tensor>& trust, double lr, double beta1,
              double beta2, double eps, double wd, int64_t step, bool bias_correction, double grad_scale,
-             const c10::optional<Tensor>& step_dev, const c10::optional<Tensor>& lr_dev) {
+             const c10::optional<Tensor>& step_dev, const c10::optional<Tensor>& lr_dev,
+             const c10::optional<Tensor>& clip, double phi_min, c10::optional<double> phi_max) {
   CHECK_DEV(table);
   CHECK_DEV(chunks);
   dcp::LambHyper h;
+  h.clip = clip_ctl_ptr(clip, "mt_lamb");
+  h.phi_min = (float)phi_min;
+  h.phi_max = phi_max.has_value() ? (float)*phi_max : INFINITY;  // None: no upper clamp
   h.step_dev = nullptr;
   h.lr_dev = nullptr;
   h.trust = nullptr;
@@ -2380,18 +2431,21 @@ TORCH_LIBRARY(dcp, m) {
       &mt_sgd);
   m.def(
       "mt_adam(Tensor table, Tensor chunks, float lr, float beta1, float beta2, float eps, float wd, int step, bool "
-      "decoupled, float grad_scale, Tensor? step_dev=None, Tensor? lr_dev=None) -> ()",
+      "decoupled, float grad_scale, Tensor? step_dev=None, Tensor? lr_dev=None, Tensor? clip=None) -> ()",
       &mt_adam);
   m.def(
       "mt_lamb(Tensor table, Tensor chunks, Tensor? spans, Tensor? partials, Tensor? trust, float lr, float beta1, "
       "float beta2, float eps, float wd, int step, bool bias_correction, float grad_scale, Tensor? step_dev=None, "
-      "Tensor? lr_dev=None) -> ()",
+      "Tensor? lr_dev=None, Tensor? clip=None, float phi_min=0.0, float? phi_max=None) -> ()",
       &mt_lamb);
   m.def(
       "mt_lars(Tensor table, Tensor chunks, Tensor? spans, Tensor? partials, Tensor? trust, float lr, float momentum, "
       "float dampening, float wd, bool nesterov, bool first, float grad_scale, float eta, float eps, Tensor? "
-      "lr_dev=None) -> ()",
+      "lr_dev=None, Tensor? clip=None, bool trust_clip=False) -> ()",
       &mt_lars);
+  m.def("mt_gnorm2(Tensor table, Tensor chunks, Tensor slots, Tensor(a!) partials, Tensor clip) -> ()", &mt_gnorm2);
+  m.def("gnorm_finish(Tensor partials, Tensor slot_gs, float max_norm, bool skip_nonfinite, Tensor(a!) clip) -> ()",
+        &gnorm_finish);
   m.def("cdr_threshold(Tensor table, Tensor chunks, Tensor state) -> Tensor", &cdr_threshold);
   m.def("mt_copy(Tensor table, Tensor chunks, float scale, int mode) -> ()", &mt_copy);
   m.def(

@@ -294,6 +294,22 @@ struct SgdHyper {
   float lr, momentum, dampening, wd, grad_scale;
   int nesterov, first;
 };
+// Device control block of global gradient-norm clipping (written by gnorm_finish, read by the update
+// kernels): the step's coefficient, whether the step is skipped (non-finite norm), the norm, the
+// running count of skipped steps, and the epoch that stamps this step's partials.  32 bytes.
+struct ClipCtl {
+  float coef;
+  int skip;
+  float norm;
+  int skipped;
+  unsigned epoch;
+  int pad[3];
+};
+// One slot of the norm's partials: a chunk's sum of g^2 and the epoch of the step that wrote it.
+struct GnormPartial {
+  float sum;
+  unsigned epoch;
+};
 struct AdamHyper {
   float lr, beta1, beta2, eps, wd, grad_scale, bc1, bc2;
   // 1 - beta and log(beta), formed in double from the caller's beta and then rounded: 1.f - (float)0.999
@@ -302,11 +318,14 @@ struct AdamHyper {
   int decoupled;
   const int* step_dev;  // optional device step count: bc1/bc2 computed in-kernel from it
   const float* lr_dev;  // optional device learning rate, read by the kernel instead of lr
+  const ClipCtl* clip;  // optional: grad_scale becomes fl(grad_scale * coef); a set skip flag writes nothing
 };
 struct LarsHyper {
   SgdHyper sgd;         // wd and grad_scale enter the scaled gradient d; the SGD update on d has no decay
   const float* trust;   // per table entry, or null: every trust ratio is 1 (a non-adaptive group)
   const float* lr_dev;  // optional device learning rate, read by the kernel instead of sgd.lr
+  const ClipCtl* clip;  // optional, as in AdamHyper
+  int trust_clip;       // LARC's clip mode: trust <- min(trust / lr, 1), 1 when lr <= 0
 };
 struct LambHyper {
   float lr, beta1, beta2, eps, wd, grad_scale;
@@ -316,7 +335,17 @@ struct LambHyper {
   const int* step_dev;     // optional device step count (bias corrections of a replayed HIP graph)
   const float* lr_dev;     // optional device learning rate
   const float* trust;      // per table entry; set by launch_mt_lamb
+  const ClipCtl* clip;     // optional, as in AdamHyper
+  float phi_min, phi_max;  // trust = clamp(|w|, phi_min, phi_max) / |u|; 0 and +inf: |w| / |u|
 };
+// Global gradient norm.  launch_mt_gnorm2: per-chunk sums of g^2 of the table's tensors into
+// partials[slots[entry] + chunk], stamped with ctl's epoch.  launch_gnorm_finish: all nslots slots
+// (each weighted with slot_gs^2, its group's grad_scale) merged into ctl's norm, coefficient
+// (max_norm > 0, else 1) and skip flag (skip_nonfinite and a non-finite norm).
+void launch_mt_gnorm2(const MTEntry* tab, const int2* chunks, int nchunks, const int* slots, const ClipCtl* ctl,
+                      GnormPartial* partials, hipStream_t s);
+void launch_gnorm_finish(const GnormPartial* partials, int nslots, const float* slot_gs, float max_norm,
+                         int skip_nonfinite, ClipCtl* ctl, hipStream_t s);
 // mode: bit 0 = source bf16, bit 1 = destination bf16 (MTEntry.p = destination, .g = source)
 void launch_mt_copy(const MTEntry* tab, const int2* chunks, int nchunks, float scale, int mode, hipStream_t s);
 void launch_mt_sgd(const MTEntry* tab, const int2* chunks, int nchunks, SgdHyper h, hipStream_t s);

@@ -15,6 +15,9 @@
 // * LAMB over the same tables and scratch: Adam's moments with the per-chunk sums of w^2 and u^2, the
 //   per-tensor trust ratio |w| / |u|, the update on the recomputed u.  Adam reads its learning rate
 //   from a device scalar too when one is given.
+// * Global gradient-norm clipping and the non-finite skip in front of Adam, LARS (FusedSGD through it)
+//   and LAMB: per-chunk sums of g^2, one workgroup that merges them into a device control block
+//   (coefficient, skip flag, norm), which every update kernel reads.
 // * CDR (CDR/main.py:186-204): threshold = k-th largest |g*w| over all 2-D/4-D
 //   parameters, found by a 4-pass 8-bit radix select over the float bit
 //   patterns (non-negative floats order like their uint32 bits) without
@@ -90,6 +93,109 @@ __global__ void __launch_bounds__(256) mt_sgd_kernel(const MTEntry* __restrict__
   }
 }
 
+
+// ---------------------------------------------------------------------------
+// Global gradient-norm clipping and the non-finite skip.
+//   norm = fl32(sqrt(sum over parameters of (grad_scale g)^2)), the sum merged in fp64
+//   coef = max_norm / (norm + 1e-6), replaced by 1 when it exceeds 1 (clip_grad_norm_'s formula)
+// The clipped step IS the plain step with grad_scale' = fl32(grad_scale coef): every update kernel
+// forms that product once (clip_scale) and uses it wherever it used grad_scale.  With the skip flag
+// set a kernel returns before it writes anything.  A null control block leaves every kernel as it was.
+// ---------------------------------------------------------------------------
+
+// wave-uniform: whether this step is skipped, and the effective grad_scale of the launch
+__device__ __forceinline__ bool clip_skip(const ClipCtl* c) { return c && c->skip != 0; }
+__device__ __forceinline__ float clip_scale(float grad_scale, const ClipCtl* c) {
+  return c ? __fmul_rn(grad_scale, c->coef) : grad_scale;
+}
+
+// One workgroup per chunk: partials[slots[entry] + chunk] = (sum g^2 of the chunk, this step's
+// epoch).  mt_norm2_kernel's ownership and order: thread t owns the chunk elements 4 (t + 256 k) + u
+// and accumulates them in that order with one fused multiply-add each, then block_sum; the 16-byte
+// path loads the same four elements as one float4.  Gradients only: 4 B / element.  The epoch stamp
+// marks the slot as written in this step: gnorm_finish counts no slot of an earlier step, so a
+// parameter without a gradient drops out of the norm without a host-side clear.
+__global__ void __launch_bounds__(256) mt_gnorm2_kernel(const MTEntry* __restrict__ tab, const int2* __restrict__ chunks,
+                                                        const int* __restrict__ slots, const ClipCtl* __restrict__ ctl,
+                                                        GnormPartial* __restrict__ partials) {
+  __shared__ float red[16];
+  const int2 ck = chunks[blockIdx.x];
+  const MTEntry e = tab[ck.x];
+  const int64_t base = (int64_t)ck.y * kChunk;
+  const int len = (int)(min(e.n, base + kChunk) - base);
+  const float* g = e.g + base;
+  float sg = 0.f;
+  if ((((uintptr_t)g) & 15u) == 0 && (len & 3) == 0) {
+    const int n4 = len >> 2;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int j = threadIdx.x + 256 * k;
+      if (j < n4) {
+        float gv[4];
+        *(float4*)gv = ((const float4*)g)[j];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sg = fmaf(gv[u], gv[u], sg);
+      }
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int i0 = 4 * (threadIdx.x + 256 * k);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        if (i0 + u < len) {
+          const float gv = g[i0 + u];
+          sg = fmaf(gv, gv, sg);
+        }
+      }
+    }
+  }
+  sg = block_sum(sg, red);
+  if (threadIdx.x == 0) {
+    GnormPartial o;
+    o.sum = sg;
+    o.epoch = ctl->epoch;
+    partials[slots[ck.x] + ck.y] = o;
+  }
+}
+
+// One workgroup: every slot of the optimizer merged in fp64 in a fixed order (thread t takes slots
+// t, t + 256, ... serially, then the shared-memory tree of merge_partials), each weighted with its
+// group's grad_scale^2; slots not stamped with this step's epoch count as zero.  The norm is rounded
+// to fp32 once; the coefficient is formed in fp32.  A NaN norm gives a NaN coefficient (the compare
+// is false, nothing is replaced).  Thread 0 then opens the next epoch.
+__global__ void __launch_bounds__(256) gnorm_finish_kernel(const GnormPartial* __restrict__ partials, int nslots,
+                                                           const float* __restrict__ slot_gs, float max_norm,
+                                                           int skip_nonfinite, ClipCtl* __restrict__ ctl) {
+  __shared__ double sh[256];
+  const unsigned epoch = ctl->epoch;
+  double a = 0.0;
+  for (int c = threadIdx.x; c < nslots; c += 256) {
+    const GnormPartial v = partials[c];
+    const double gs = (double)slot_gs[c];
+    if (v.epoch == epoch) a += gs * gs * (double)v.sum;
+  }
+  sh[threadIdx.x] = a;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const float norm = (float)sqrt(sh[0]);
+    float coef = 1.f;
+    if (max_norm > 0.f) {
+      coef = __fdiv_rn(max_norm, __fadd_rn(norm, 1e-6f));
+      if (coef > 1.f) coef = 1.f;
+    }  // max_norm 0: the norm is computed for the skip flag only
+    const int skip = (skip_nonfinite && !(fabsf(norm) <= 3.402823466e+38f)) ? 1 : 0;
+    ctl->coef = coef;
+    ctl->skip = skip;
+    ctl->norm = norm;
+    ctl->skipped += skip;
+    ctl->epoch = epoch + 1u;
+  }
+}
 
 // ---------------------------------------------------------------------------
 // LARS (layer-wise adaptive rate scaling; You, Gitman, Ginsburg 2017), "scaled gradient into SGD":
@@ -176,14 +282,23 @@ __device__ __forceinline__ void merge_partials(const int2 sp, const float2* __re
 
 __global__ void __launch_bounds__(256) lars_trust_kernel(const int2* __restrict__ spans, const float2* __restrict__ partials,
                                                          float grad_scale, float wd, float eta, float eps,
-                                                         float* __restrict__ trust) {
+                                                         float* __restrict__ trust, LarsHyper lh) {
   __shared__ double sh[2][256];
+  if (clip_skip(lh.clip)) return;  // a skipped step keeps the last step's ratios
+  grad_scale = clip_scale(grad_scale, lh.clip);
   merge_partials(spans[blockIdx.x], partials, sh);  // spans: (first chunk, number of chunks)
   if (threadIdx.x == 0) {
     const float wn = (float)sqrt(sh[0][0]);
     const float gn = (float)(fabs((double)grad_scale) * sqrt(sh[1][0]));
     float t = 1.f;
-    if (wn > 0.f && gn > 0.f) t = eta * wn / (fmaf(wd, wn, gn) + eps);
+    if (wn > 0.f && gn > 0.f) {
+      t = eta * wn / (fmaf(wd, wn, gn) + eps);
+      if (lh.trust_clip) {  // LARC's clip mode: the local rate lr * t never exceeds lr
+        const float lr = lh.lr_dev ? *lh.lr_dev : lh.sgd.lr;
+        t = lr > 0.f ? __fdiv_rn(t, lr) : 1.f;
+        if (t > 1.f) t = 1.f;
+      }
+    }
     trust[blockIdx.x] = t;
   }
 }
@@ -204,8 +319,9 @@ __global__ void __launch_bounds__(256) mt_lars_kernel(const MTEntry* __restrict_
   const MTEntry e = tab[ck.x];
   const int64_t base = (int64_t)ck.y * kChunk;
   const int64_t end = min(e.n, base + kChunk);
+  if (clip_skip(lh.clip)) return;
   SgdHyper h = lh.sgd;
-  const float gs = h.grad_scale, wd = h.wd;
+  const float gs = clip_scale(h.grad_scale, lh.clip), wd = h.wd;
   h.grad_scale = 1.f;
   h.wd = 0.f;
   if (lh.lr_dev) h.lr = *lh.lr_dev;
@@ -263,8 +379,10 @@ __global__ void __launch_bounds__(256) mt_adam_kernel(const MTEntry* __restrict_
   }
   const float rbc2 = 1.f / sqrtf(bc2);
   const float lr = h.lr_dev ? *h.lr_dev : h.lr;  // the device scalar: a replayed graph follows a schedule
+  if (clip_skip(h.clip)) return;
+  const float gs = clip_scale(h.grad_scale, h.clip);
   for (int64_t i = base + threadIdx.x; i < end; i += blockDim.x) {
-    float g = e.g[i] * h.grad_scale;
+    float g = e.g[i] * gs;
     float p = e.p[i];
     if (h.wd != 0.f) {
       if (h.decoupled)
@@ -309,8 +427,8 @@ __device__ __forceinline__ void lamb_bias(const LambHyper& h, float& bc1, float&
 // One element's moments and its u.  Every operation is named (no bare a * b + c for the compiler to
 // contract one way in the 16-byte loop and another in the 4-byte loop): both loops, and both
 // kernels, round alike.
-__device__ __forceinline__ void lamb_moments(float gin, float& m, float& v, const LambHyper& h) {
-  const float g = __fmul_rn(gin, h.grad_scale);
+__device__ __forceinline__ void lamb_moments(float gin, float gs, float& m, float& v, const LambHyper& h) {
+  const float g = __fmul_rn(gin, gs);
   m = fmaf(h.beta1, m, __fmul_rn(h.omb1, g));
   v = fmaf(h.beta2, v, __fmul_rn(h.omb2, __fmul_rn(g, g)));
 }
@@ -338,6 +456,8 @@ __global__ void __launch_bounds__(256) mt_lamb_moments_kernel(const MTEntry* __r
   float* m = e.s1 + base;
   float* v = e.s2 + base;
   bf16* shadow = (APPLY && e.shadow) ? e.shadow + base : nullptr;
+  if (clip_skip(h.clip)) return;  // whole workgroups: no barrier is left waiting
+  const float gs = clip_scale(h.grad_scale, h.clip);
   float bc1, rbc2;
   lamb_bias(h, bc1, rbc2);
   const float nlr = APPLY ? -(h.lr_dev ? *h.lr_dev : h.lr) : 0.f;
@@ -357,7 +477,7 @@ __global__ void __launch_bounds__(256) mt_lamb_moments_kernel(const MTEntry* __r
         *(float4*)vv = ((const float4*)v)[j];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          lamb_moments(gv[u], mv[u], vv[u], h);
+          lamb_moments(gv[u], gs, mv[u], vv[u], h);
           const float uu = lamb_u(mv[u], vv[u], pv[u], bc1, rbc2, h);
           if (APPLY) {
             pv[u] = fmaf(nlr, uu, pv[u]);
@@ -388,7 +508,7 @@ __global__ void __launch_bounds__(256) mt_lamb_moments_kernel(const MTEntry* __r
         const int i = i0 + u;
         if (i < len) {
           float pv = p[i], mv = m[i], vv = v[i];
-          lamb_moments(g[i], mv, vv, h);
+          lamb_moments(g[i], gs, mv, vv, h);
           const float uu = lamb_u(mv, vv, pv, bc1, rbc2, h);
           m[i] = mv;
           v[i] = vv;
@@ -414,13 +534,16 @@ __global__ void __launch_bounds__(256) mt_lamb_moments_kernel(const MTEntry* __r
 // One workgroup per tensor: lars_trust_kernel's merge; |w| and |u| rounded to fp32 once each, the
 // ratio formed in fp32.
 __global__ void __launch_bounds__(256) lamb_trust_kernel(const int2* __restrict__ spans, const float2* __restrict__ partials,
-                                                         float* __restrict__ trust) {
+                                                         float* __restrict__ trust, const ClipCtl* __restrict__ clip,
+                                                         float phi_min, float phi_max) {
   __shared__ double sh[2][256];
+  if (clip_skip(clip)) return;  // a skipped step left no partials: the last step's ratios stay
   merge_partials(spans[blockIdx.x], partials, sh);
   if (threadIdx.x == 0) {
     const float wn = (float)sqrt(sh[0][0]);
     const float un = (float)sqrt(sh[1][0]);
-    trust[blockIdx.x] = (wn > 0.f && un > 0.f) ? __fdiv_rn(wn, un) : 1.f;
+    // the paper's phi: |w| clamped to [phi_min, phi_max] (0 and +inf leave every positive |w| as it is)
+    trust[blockIdx.x] = (wn > 0.f && un > 0.f) ? __fdiv_rn(fminf(fmaxf(wn, phi_min), phi_max), un) : 1.f;
   }
 }
 
@@ -432,9 +555,10 @@ __global__ void __launch_bounds__(256) mt_lamb_update_kernel(const MTEntry* __re
   const MTEntry e = tab[ck.x];
   const int64_t base = (int64_t)ck.y * kChunk;
   const int64_t end = min(e.n, base + kChunk);
+  if (clip_skip(h.clip)) return;
   float bc1, rbc2;
   lamb_bias(h, bc1, rbc2);
-  const float nlt = -__fmul_rn(h.lr_dev ? *h.lr_dev : h.lr, h.trust[ck.x]);
+  const float nlt =-__fmul_rn(h.lr_dev ? *h.lr_dev : h.lr, h.trust[ck.x]);
   const uintptr_t mis = ((uintptr_t)(e.p + base) | (uintptr_t)(e.s1 + base) | (uintptr_t)(e.s2 + base)) & 15u;
   const uintptr_t smis = e.shadow ? ((uintptr_t)(e.shadow + base) & 7u) : 0;
   if (mis == 0 && smis == 0 && ((end - base) & 3) == 0) {
@@ -569,7 +693,7 @@ void launch_mt_lars(const MTEntry* tab, const int2* chunks, int nchunks, const i
   if (trust) {  // adaptive: the update reads the trust ratios this step's norms give
     hipLaunchKernelGGL(mt_norm2_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, partials);
     hipLaunchKernelGGL(lars_trust_kernel, dim3(ntensors), dim3(256), 0, s, spans, partials, h.sgd.grad_scale,
-                       h.sgd.wd, eta, eps, trust);
+                       h.sgd.wd, eta, eps, trust, h);
   }
   h.trust = trust;
   hipLaunchKernelGGL(mt_lars_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, h);
@@ -586,8 +710,18 @@ void launch_mt_lamb(const MTEntry* tab, const int2* chunks, int nchunks, const i
     return;
   }
   hipLaunchKernelGGL((mt_lamb_moments_kernel<false>), dim3(nchunks), dim3(256), 0, s, tab, chunks, partials, h);
-  hipLaunchKernelGGL(lamb_trust_kernel, dim3(ntensors), dim3(256), 0, s, spans, partials, trust);
+  hipLaunchKernelGGL(lamb_trust_kernel, dim3(ntensors), dim3(256), 0, s, spans, partials, trust, h.clip, h.phi_min,
+                     h.phi_max);
   hipLaunchKernelGGL(mt_lamb_update_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, h);
+}
+void launch_mt_gnorm2(const MTEntry* tab, const int2* chunks, int nchunks, const int* slots, const ClipCtl* ctl,
+                      GnormPartial* partials, hipStream_t s) {
+  if (nchunks) hipLaunchKernelGGL(mt_gnorm2_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, slots, ctl, partials);
+}
+void launch_gnorm_finish(const GnormPartial* partials, int nslots, const float* slot_gs, float max_norm,
+                         int skip_nonfinite, ClipCtl* ctl, hipStream_t s) {
+  hipLaunchKernelGGL(gnorm_finish_kernel, dim3(1), dim3(256), 0, s, partials, nslots, slot_gs, max_norm, skip_nonfinite,
+                     ctl);
 }
 void launch_cdr_threshold(const MTEntry* tab, const int2* chunks, int nchunks, uint32_t* state, uint32_t* hist,
                           hipStream_t s) {

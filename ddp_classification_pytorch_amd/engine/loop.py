@@ -265,9 +265,14 @@ class ClassificationLoop:
                     f"top1 {100 * w[1] / max(w[3], 1):.2f} top3 {100 * w[2] / max(w[3], 1):.2f} lr {lr:.3g} "
                     f"{(i + 1) * B * self.rt.world / max(dt, 1e-9):.0f} img/s "
                     f"eta {eta:.0f}s")
+                clip = {}
+                if getattr(self.optimizer, "needs_global_norm", False) and self.optimizer.grad_norm() is not None:
+                    # the last step's values (the window's metrics were just synchronised above)
+                    clip = dict(grad_norm=float(self.optimizer.grad_norm()), clip_coef=float(self.optimizer.clip_coef()),
+                                skipped_steps=int(self.optimizer.skipped_steps()))
                 self.logger.log("train_iter", epoch=epoch, step=self.global_step, loss=w[0] / max(w[3], 1),
                                 top1=w[1] / max(w[3], 1), top3=w[2] / max(w[3], 1), lr=lr, gpu_ms_per_step=gpu_ms,
-                                img_per_s=win_ips)
+                                img_per_s=win_ips, **clip)
                 win.zero_()
         if prof is not None:
             prof.__exit__(None, None, None)

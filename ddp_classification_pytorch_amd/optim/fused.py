@@ -24,6 +24,9 @@ per-iteration schedule.
 :class:`FusedLARS` (layer-wise adaptive rate scaling for large global batches) adds a per-tensor
 trust ratio in front of the SGD update (``mt_lars``), :class:`FusedLAMB` one in front of Adam's
 (``mt_lamb``); both always read their learning rate from the device.
+
+All four take ``max_grad_norm`` / ``skip_nonfinite``: global gradient-norm clipping and the non-finite
+skip, computed on the device and read by the update kernels (:class:`_GradClip`).
 """
 from __future__ import annotations
 
@@ -110,9 +113,204 @@ class _DeviceLR:
             ent[1] = None  # the (loaded) learning rates are written at the next push
 
 
-class FusedSGD(_DeviceLR, torch.optim.Optimizer):
+class _ClipState:
+    """Device state of one optimizer's clipping: the control block (float32[8]: coefficient, skip flag,
+    norm, skipped count, epoch; see ``ClipCtl`` in csrc/launchers.h), the partials (one slot per
+    4096-element chunk of every parameter) and each slot's ``grad_scale``."""
+
+    def __init__(self):
+        self.sig = None          # numels per group: the slot layout depends on nothing else
+        self.ctl = None
+        self.partials = self.slot_gs = None
+        self.slot0 = {}          # id(param) -> its first slot
+        self.gs = None           # the groups' grad_scale last written to slot_gs
+        self.spans = []          # (first slot, slot count) per group
+        self.tables = {}
+        self.fast = {}           # launch key -> (pointer fingerprint, table, chunks, slots)
+
+
+class _GradClip:
+    """Global gradient-norm clipping and the non-finite skip of the fused optimizers.
+
+        norm = fl32(sqrt(sum over every parameter with a gradient of (grad_scale * g)^2))   (fp64 sum)
+        coef = max_grad_norm / (norm + 1e-6)  in fp32, replaced by 1 when it exceeds 1
+        the step = the plain step with grad_scale' = fl32(grad_scale * coef), and nothing else
+
+    which is ``torch.nn.utils.clip_grad_norm_`` in front of the step.  The norm is global over all
+    groups of ONE optimizer: a workload that builds two optimizers clips each on its own.  With
+    ``skip_nonfinite`` a step whose norm is inf or NaN changes no parameter, momentum buffer, moment
+    or trust ratio (``max_grad_norm=0`` then computes the norm for the flag only, coefficient 1).
+    Adam's and LAMB's bias-correction step count still advances on a skipped step, on the device and
+    on the host -- the host cannot know about the skip without a sync -- unlike a GradScaler-skipped
+    ``torch.optim.Adam`` step, which leaves the count alone.  A skipped FIRST step of a momentum
+    buffer leaves it zero and the next step treats it as an ordinary one (identical with dampening 0).
+
+    GPU: ``mt_gnorm2`` writes one fp32 sum of g^2 per chunk into that parameter's fixed slots (ordered
+    by group and position in the group, so the merge order and the bits of the norm do not depend on
+    the entry point or launch order), ``gnorm_finish`` merges them in fp64 into the control block
+    that every update kernel reads.  Nothing is read on the host: a captured step clips, does not
+    clip, or skips from replay to replay purely from the data.  The control block is created by an
+    eager step before capture, like the device learning rate.
+
+    The bucket engine calls :meth:`norm_params` per bucket behind its all-reduce and
+    :meth:`step_after_norms` once at the end of backward (``needs_global_norm`` selects that route).
+    """
+
+    needs_global_norm = False
+
+    def _init_clip(self, max_grad_norm, skip_nonfinite):
+        if not max_grad_norm >= 0:
+            raise ValueError("max_grad_norm must be >= 0 (0: no clipping)")
+        self.max_grad_norm = float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.needs_global_norm = self.max_grad_norm > 0 or self.skip_nonfinite
+        self._clip = _ClipState()
+        self._cpu_sums = {}      # CPU: id(param) -> fp64 sum of g^2 of this step
+        self._cpu_clip = None    # CPU: (coef, skip, norm, skipped count) of the last step
+
+    # ---------------------------------------------------------------- accessors (no sync)
+    def _clip_field(self, i, as_int=False):
+        if self._cpu_clip is not None:
+            return self._cpu_clip[i]
+        ctl = self._clip.ctl
+        if ctl is None:
+            return None
+        return (ctl.view(torch.int32) if as_int else ctl)[i]
+
+    def grad_norm(self):
+        """The global gradient norm of the last step as a device scalar view; None before it."""
+        return self._clip_field(2)
+
+    def clip_coef(self):
+        """The coefficient the last step applied (1: not clipped; NaN: a NaN norm without skipping)."""
+        return self._clip_field(0)
+
+    def skipped_steps(self):
+        """The running count of skipped steps (int32 device scalar view; diagnostic, not checkpointed)."""
+        return self._clip_field(3, as_int=True)
+
+    # ---------------------------------------------------------------- device state
+    def _clip_state(self, device):
+        st = self._clip
+        sig = tuple(tuple(p.numel() for p in g["params"]) for g in self.param_groups)
+        if st.sig != sig:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{type(self).__name__}: the clipping control block must be created by an eager "
+                                   "step before capture")
+            if st.ctl is None:
+                st.ctl = torch.zeros(8, dtype=torch.float32, device=device)
+                st.ctl[0] = 1.0
+                st.ctl.view(torch.int32)[4] = 1  # epoch 1: the zeroed partials belong to no step
+            acc, st.slot0, st.spans = 0, {}, []
+            for g in self.param_groups:
+                first = acc
+                for p in g["params"]:
+                    st.slot0[id(p)] = acc
+                    acc += (p.numel() + CHUNK - 1) // CHUNK
+                st.spans.append((first, acc - first))
+            st.partials = torch.zeros(max(acc, 1), 2, dtype=torch.float32, device=device)
+            st.sig, st.gs = sig, None
+            st.tables.clear()
+            st.fast.clear()
+        gs = tuple(float(g["grad_scale"]) for g in self.param_groups)
+        if st.gs != gs:
+            per_slot = torch.cat([torch.full((max(n, 0),), v, dtype=torch.float32) for (_, n), v in zip(st.spans, gs)]
+                                 + [torch.zeros(1, dtype=torch.float32)])[:st.partials.shape[0]]
+            # through the fill kernel's arguments (graph-capture safe): the float bits as int32
+            st.slot_gs = Fn.table_to_device(per_slot.view(torch.int32), torch.int32, device).view(torch.float32)
+            st.gs = gs
+        return st
+
+    def _clip_ctl(self):
+        # the norm pass of this step created it (no parameter with a gradient: nothing launches either)
+        return self._clip.ctl if self.needs_global_norm else None
+
+    def _own_with_grad(self, params=None):
+        if params is None:
+            return [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        gid = FusedSGD._group_index(self)
+        return [p for p in params if id(p) in gid and p.grad is not None]
+
+    @torch.no_grad()
+    def norm_params(self, params):
+        """The norm pass for ``params`` (one bucket, behind its all-reduce): their chunks' sums of g^2
+        into their slots.  Any partition of the parameters, in any order, gives the same norm bits."""
+        params = self._own_with_grad(params)
+        if not params:
+            return
+        if not params[0].is_cuda:
+            for p in params:
+                g = p.grad.detach().to(torch.float64)
+                self._cpu_sums[id(p)] = (g * g).sum()
+            return
+        name = type(self).__name__
+        dev = params[0].device
+        st = self._clip_state(dev)
+        key = (len(params), params[0].data_ptr())
+        fp = tuple((id(p), p.grad.data_ptr()) for p in params)
+        hit = st.fast.get(key)
+        if hit is None or hit[0] != fp:
+            entries = []
+            for p in params:
+                if not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
+                    raise RuntimeError(f"{name} needs contiguous fp32 grads")
+                entries.append((p.data_ptr(), p.grad.data_ptr(), 0, 0, 0, p.numel()))
+            table, chunks = st.tables.setdefault(key, _TableCache()).get(entries, dev)
+            slots = Fn.table_to_device([st.slot0[id(p)] for p in params], torch.int32, dev)
+            hit = st.fast[key] = (fp, table, chunks, slots)
+        _ext.hip_ops().mt_gnorm2(hit[1], hit[2], hit[3], st.partials, st.ctl)
+
+    def _finish_norm(self):
+        """Merge this step's partials into the norm, the coefficient and the skip flag."""
+        ps = [p for g in self.param_groups for p in g["params"]]
+        if not ps:
+            return
+        if ps[0].is_cuda:
+            st = self._clip_state(ps[0].device)
+            _ext.hip_ops().gnorm_finish(st.partials, st.slot_gs, self.max_grad_norm, self.skip_nonfinite, st.ctl)
+            return
+        total = torch.zeros((), dtype=torch.float64)
+        for g in self.param_groups:  # the fixed order: by group, by position in the group
+            gs = float(torch.tensor(g["grad_scale"], dtype=torch.float32))
+            for p in g["params"]:
+                s = self._cpu_sums.get(id(p))
+                if s is not None:
+                    total = total + gs * gs * s
+        self._cpu_sums = {}
+        norm = total.sqrt().to(torch.float32)
+        coef = torch.ones((), dtype=torch.float32)
+        if self.max_grad_norm > 0:
+            coef = torch.tensor(self.max_grad_norm, dtype=torch.float32) / (norm + torch.tensor(1e-6, dtype=torch.float32))
+            if coef > 1:
+                coef = torch.ones((), dtype=torch.float32)
+        skip = bool(self.skip_nonfinite and not torch.isfinite(norm))
+        count = (int(self._cpu_clip[3]) if self._cpu_clip is not None else 0) + int(skip)
+        self._cpu_clip = (coef, skip, norm, torch.tensor(count, dtype=torch.int32))
+
+    def _cpu_gs(self, group):
+        """CPU path: the group's effective grad_scale, fl32(grad_scale * coef) under clipping."""
+        gs = group["grad_scale"]
+        if not self.needs_global_norm or self._cpu_clip is None:
+            return gs
+        return float(torch.tensor(gs, dtype=torch.float32) * self._cpu_clip[0])
+
+    def _cpu_skip(self):
+        return self.needs_global_norm and self._cpu_clip is not None and self._cpu_clip[1]
+
+    def _norm_all(self):
+        if self.needs_global_norm:
+            self.norm_params(None)
+            self._finish_norm()
+
+    def _no_bucket_steps(self):
+        if self.needs_global_norm:
+            raise RuntimeError(f"{type(self).__name__}: a global gradient norm needs every gradient before any "
+                               "update; use norm_params() per bucket and step_after_norms() instead of step_params()")
+
+
+class FusedSGD(_GradClip, _DeviceLR, torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 grad_scale=1.0, device_lr=False):
+                 grad_scale=1.0, device_lr=False, max_grad_norm=0.0, skip_nonfinite=False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
@@ -123,6 +321,7 @@ class FusedSGD(_DeviceLR, torch.optim.Optimizer):
         self._gid = None         # id(param) -> group index (step_params), rebuilt when groups change
         self._reducer_stepped = False
         self._init_device_lr(device_lr)
+        self._init_clip(max_grad_norm, skip_nonfinite)
 
     def mark_stepped_by_reducer(self):
         """The bucket engine (parallel/reducer.py) already applied this step per bucket: the next
@@ -152,9 +351,19 @@ class FusedSGD(_DeviceLR, torch.optim.Optimizer):
             return loss
         if self.device_lr and not _capturing():
             self.push_lr()
+        self._norm_all()
         self._step_subset(None)
         Fn.bump_weight_generation()
         return loss
+
+    @torch.no_grad()
+    def step_after_norms(self):
+        """The bucket engine's end of backward under clipping: every bucket's :meth:`norm_params` has
+        run; merge the norm, then update every parameter that has a gradient."""
+        if self.device_lr and not _capturing():
+            self.push_lr()
+        self._finish_norm()
+        self._step_subset(None)
 
     @torch.no_grad()
     def step_params(self, params):
@@ -162,6 +371,7 @@ class FusedSGD(_DeviceLR, torch.optim.Optimizer):
         hyper-parameters apply to its own members.  The caller bumps the weight generation.
         Host cost is O(len(params)): the bucket's members are grouped by a cached param -> group
         map instead of scanning every group (the bucket engine calls this once per bucket)."""
+        self._no_bucket_steps()
         if self.device_lr and not _capturing():
             self.push_lr()
         gid = self._group_index()
@@ -222,8 +432,10 @@ class FusedSGD(_DeviceLR, torch.optim.Optimizer):
                 self._fast[key] = (fp, table, chunks)
             self._launch(gi, group, table, chunks, first)
             return
+        if self._cpu_skip():
+            return
         for p in params:
-            g = p.grad * group["grad_scale"]
+            g = p.grad * self._cpu_gs(group)
             if group["weight_decay"]:
                 g = g + group["weight_decay"] * p
             if mom:
@@ -236,25 +448,27 @@ class FusedSGD(_DeviceLR, torch.optim.Optimizer):
             p.add_(g, alpha=-group["lr"])
 
     def _launch(self, gi, group, table, chunks, first):
-        if self.device_lr:
+        if self.device_lr or self.needs_global_norm:
             # mt_lars without a trust table is the mt_sgd step, bit for bit, with the rate read from the device
+            # and / or the clipping control block applied
             _ext.hip_ops().mt_lars(table, chunks, None, None, None, group["lr"], group["momentum"], group["dampening"],
                                    group["weight_decay"], group["nesterov"], first, group["grad_scale"], 0.0, 0.0,
-                                   self._lr_tensor(gi, group, table.device))
+                                   self._lr_tensor(gi, group, table.device) if self.device_lr else None,
+                                   self._clip_ctl())
             return
         _ext.hip_ops().mt_sgd(table, chunks, group["lr"], group["momentum"], group["dampening"], group["weight_decay"],
                               group["nesterov"], first, group["grad_scale"])
 
 
-class FusedAdam(_DeviceLR, torch.optim.Optimizer):
+class FusedAdam(_GradClip, _DeviceLR, torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False,
-                 grad_scale=1.0, device_lr=False):
+                 grad_scale=1.0, device_lr=False, max_grad_norm=0.0, skip_nonfinite=False):
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, decoupled=decoupled,
                         grad_scale=grad_scale)
         super().__init__(params, defaults)
-        self._init_runtime(device_lr)
+        self._init_runtime(device_lr, max_grad_norm, skip_nonfinite)
 
-    def _init_runtime(self, device_lr):
+    def _init_runtime(self, device_lr, max_grad_norm=0.0, skip_nonfinite=False):
         self._tables = {}
         self._dsteps = {}        # launch key -> [device int32 step, host mirror, params]
         self._captured = None    # launch keys of the step being / last captured into a HIP graph
@@ -262,6 +476,7 @@ class FusedAdam(_DeviceLR, torch.optim.Optimizer):
         self._bucket_capture_open = False
         self._gid = None
         self._init_device_lr(device_lr)
+        self._init_clip(max_grad_norm, skip_nonfinite)
 
     def mark_stepped_by_reducer(self):
         self._reducer_stepped = True
@@ -298,13 +513,25 @@ class FusedAdam(_DeviceLR, torch.optim.Optimizer):
             self._captured = []
         elif self.device_lr:
             self.push_lr()
+        self._norm_all()
         self._step_subset(None)
         Fn.bump_weight_generation()
         return loss
 
     @torch.no_grad()
+    def step_after_norms(self):
+        """See FusedSGD.step_after_norms."""
+        if _capturing():
+            self._captured = []  # this capture's launch keys
+        elif self.device_lr:
+            self.push_lr()
+        self._finish_norm()
+        self._step_subset(None)
+
+    @torch.no_grad()
     def step_params(self, params):
         """Update only ``params`` (one bucket of the bucket engine); see FusedSGD.step_params."""
+        self._no_bucket_steps()
         capturing = _capturing()
         if capturing and not self._bucket_capture_open:
             self._captured = []  # the first bucket of a captured backward: this capture's launch keys
@@ -369,12 +596,14 @@ class FusedAdam(_DeviceLR, torch.optim.Optimizer):
             table, chunks = self._tables.setdefault(key, _TableCache()).get(entries, dev)
             _ext.hip_ops().mt_adam(table, chunks, group["lr"], b1, b2, group["eps"], group["weight_decay"], step,
                                    group["decoupled"], group["grad_scale"], self._device_step(key, step, params),
-                                   self._lr_tensor(gi, group, dev) if self.device_lr else None)
+                                   self._lr_tensor(gi, group, dev) if self.device_lr else None, self._clip_ctl())
+            return
+        if self._cpu_skip():
             return
         bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
         for p in params:
             st = self.state[p]
-            g = p.grad * group["grad_scale"]
+            g = p.grad * self._cpu_gs(group)
             if group["weight_decay"]:
                 if group["decoupled"]:
                     p.mul_(1 - group["lr"] * group["weight_decay"])
@@ -429,10 +658,15 @@ class FusedLARS(FusedSGD):
     ``group["lr"]`` stays the host truth (schedulers, checkpoints, logging); :meth:`push_lr` writes
     it to the device when it changed.  A HIP-graph replay therefore follows a per-iteration schedule
     without recapture: change ``group["lr"]``, call ``push_lr()``, replay.
+
+    ``trust_clip=True`` is LARC's clip mode: an adaptive ratio becomes ``min(trust / lr, 1)`` (``lr`` read
+    from the device; 1 when ``lr <= 0``), so the layer's rate ``lr * trust`` is ``min(eta |w| / ..., lr)``.
+    ``max_grad_norm`` / ``skip_nonfinite``: see :class:`_GradClip`.
     """
 
     def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False,
-                 grad_scale=1.0, eta=1e-3, eps=1e-8, adapt=True):
+                 grad_scale=1.0, eta=1e-3, eps=1e-8, adapt=True, max_grad_norm=0.0, skip_nonfinite=False,
+                 trust_clip=False):
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         defaults = dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
@@ -443,6 +677,8 @@ class FusedLARS(FusedSGD):
         self._gid = None
         self._reducer_stepped = False
         self._init_device_lr(True)   # push_lr / _lr_tensor: see _DeviceLR
+        self._init_clip(max_grad_norm, skip_nonfinite)
+        self.trust_clip = bool(trust_clip)
         self._trust = {}         # id(param) -> (trust tensor, index) of its last step
         self._ones = {}          # device -> float32[1] of 1.0 (trust_of for non-adaptive groups)
         self._via = "step"       # which entry point is stepping: part of the launch key
@@ -461,6 +697,11 @@ class FusedLARS(FusedSGD):
     def step_params(self, params):
         self._via = "bucket"
         super().step_params(params)
+
+    @torch.no_grad()
+    def step_after_norms(self):
+        self._via = "bucket"
+        super().step_after_norms()
 
     def _update(self, gi, group, params, first):
         mom, wd, gs = group["momentum"], group["weight_decay"], group["grad_scale"]
@@ -498,9 +739,12 @@ class FusedLARS(FusedSGD):
             _ext.hip_ops().mt_lars(tabs.table, tabs.chunks, tabs.spans if adapt else None,
                                    tabs.partials if adapt else None, tabs.trust if adapt else None, group["lr"], mom,
                                    group["dampening"], wd, group["nesterov"], first, gs, group["eta"], group["eps"],
-                                   lr_dev)
+                                   lr_dev, self._clip_ctl(), self.trust_clip)
             return
         # CPU: the same formulas in fp32 (norms merged in fp64, as the trust kernel does)
+        if self._cpu_skip():
+            return
+        gs = self._cpu_gs(group)
         for p in params:
             g = p.grad * gs
             trust = torch.ones((), dtype=torch.float32)
@@ -509,6 +753,9 @@ class FusedLARS(FusedSGD):
                 gn = ((p.grad * p.grad).sum(dtype=torch.float64).sqrt() * abs(gs)).float()
                 if wn > 0 and gn > 0:
                     trust = group["eta"] * wn / (wd * wn + gn + group["eps"])
+                    if self.trust_clip:
+                        lr32 = torch.tensor(group["lr"], dtype=torch.float32)
+                        trust = torch.clamp(trust / lr32, max=1.0) if lr32 > 0 else torch.ones((), dtype=torch.float32)
             self._trust[id(p)] = trust
             if wd:
                 g = g + wd * p
@@ -539,14 +786,21 @@ class FusedLAMB(FusedAdam):
     non-adaptive group takes one.  No float atomics: a step is bit-reproducible.  The learning rate is
     always read from the device (see :class:`_DeviceLR`), the bias corrections from FusedAdam's device
     step counter: one captured HIP graph follows both.
+
+    ``phi_min`` / ``phi_max`` are the paper's phi: ``trust = clamp(|w|, phi_min, phi_max) / |u|`` (the
+    defaults 0 and +inf leave ``|w| / |u|``).  ``max_grad_norm`` / ``skip_nonfinite``: see :class:`_GradClip`.
     """
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, grad_scale=1.0,
-                 bias_correction=True, adapt=True):
+                 bias_correction=True, adapt=True, max_grad_norm=0.0, skip_nonfinite=False, phi_min=0.0,
+                 phi_max=math.inf):
+        if not 0 <= phi_min <= phi_max:
+            raise ValueError("FusedLAMB needs 0 <= phi_min <= phi_max")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, grad_scale=grad_scale,
                         bias_correction=bias_correction, adapt=adapt)
         torch.optim.Optimizer.__init__(self, params, defaults)
-        self._init_runtime(True)
+        self._init_runtime(True, max_grad_norm, skip_nonfinite)
+        self.phi_min, self.phi_max = float(phi_min), float(phi_max)
         self._trust = {}         # id(param) -> trust ratio (device scalar view) of its last step
         self._trust_src = {}     # launch key -> what self._trust was last filled from
         self._ones = {}          # device -> float32 scalar 1.0 (trust_of for non-adaptive groups)
@@ -563,6 +817,11 @@ class FusedLAMB(FusedAdam):
     def step_params(self, params):
         self._via = "bucket"
         super().step_params(params)
+
+    @torch.no_grad()
+    def step_after_norms(self):
+        self._via = "bucket"
+        super().step_after_norms()
 
     def _update(self, gi, group, params, step):
         b1, b2 = group["betas"]
@@ -598,9 +857,13 @@ class FusedLAMB(FusedAdam):
             _ext.hip_ops().mt_lamb(tabs.table, tabs.chunks, tabs.spans if adapt else None,
                                    tabs.partials if adapt else None, tabs.trust if adapt else None, group["lr"], b1, b2,
                                    eps, wd, step, bias, gs, self._device_step(key, step, params),
-                                   self._lr_tensor(gi, group, dev))
+                                   self._lr_tensor(gi, group, dev), self._clip_ctl(), self.phi_min,
+                                   None if math.isinf(self.phi_max) else self.phi_max)
             return
         # CPU: the same formulas in fp32 (norms merged in fp64, as the trust kernel does)
+        if self._cpu_skip():
+            return
+        gs = self._cpu_gs(group)
         bc1, bc2 = (1 - b1 ** step, 1 - b2 ** step) if bias else (1.0, 1.0)
         for p in params:
             st = self.state[p]
@@ -615,6 +878,6 @@ class FusedLAMB(FusedAdam):
                 wn = (p.detach() * p.detach()).sum(dtype=torch.float64).sqrt().float()
                 un = (u * u).sum(dtype=torch.float64).sqrt().float()
                 if wn > 0 and un > 0:
-                    trust = wn / un
+                    trust = torch.clamp(wn, min=self.phi_min, max=self.phi_max) / un
             self._trust[id(p)] = trust
             p.add_(u, alpha=-float(torch.tensor(group["lr"], dtype=torch.float32) * trust))

@@ -21,6 +21,11 @@ bucket", §5.8 items 1-3):
 * ``p.grad`` becomes a view into the (reduced) bucket buffer, like DDP's
   ``gradient_as_bucket_view``, so code that reads gradients after backward (CDR's global top-k
   mask, which therefore runs without the fused optimizer) sees the averaged values;
+* an optimizer that clips by the global gradient norm (``needs_global_norm``) cannot update per
+  bucket: behind each all-reduce runs its norm pass for that bucket (``norm_params``), and the
+  end of backward merges the norm and issues every update (``step_after_norms``), still on the
+  communication stream.  Bucket views hold gradients already averaged over ranks, so every rank
+  computes the same norm bits and the same coefficient, and the replicas stay identical;
 * at the end of backward (an autograd final callback) the compute stream joins the
   communication stream.  Everything is stream-ordered, no host sync: a whole step -- SyncBN
   collectives included -- can be captured into a HIP graph and replayed (engine/graph.py);
@@ -340,10 +345,32 @@ class BucketReducer:
         if self.cuda:
             with torch.cuda.stream(_comm_stream(self.device, self.world)):
                 for o, ps in by_opt.values():
-                    o.step_params(ps)
+                    self._bucket_step(o, ps)
         else:
             for o, ps in by_opt.values():
-                o.step_params(ps)
+                self._bucket_step(o, ps)
+
+    @staticmethod
+    def _bucket_step(o, ps):
+        # An optimizer that clips by the global gradient norm needs every bucket reduced before any
+        # update: behind the bucket's all-reduce runs only its norm pass (still overlapped with
+        # backward); the updates follow from _finalize (step_after_norms).
+        if getattr(o, "needs_global_norm", False):
+            o.norm_params(ps)
+        else:
+            o.step_params(ps)
+
+    def _step_after_norms(self):
+        late = [o for o in self.optimizers if getattr(o, "needs_global_norm", False)]
+        if not late:
+            return
+        if self.cuda:
+            with torch.cuda.stream(_comm_stream(self.device, self.world)):
+                for o in late:
+                    o.step_after_norms()
+        else:
+            for o in late:
+                o.step_after_norms()
 
     def _finalize(self):
         if not self._rebuilt:
@@ -351,6 +378,7 @@ class BucketReducer:
         for b in self.buckets:  # the rest (unused parameters, the first backward) in index order
             if not b.launched:
                 self._launch(b)
+        self._step_after_norms()  # on the comm stream, before the compute stream joins it
         if self.cuda:
             comm = _comm_stream(self.device, self.world)
             if self._ev is not None:

@@ -1,7 +1,7 @@
 """Step time of the fused optimizers over ResNet-50's parameter tensors (25.6M elements): FusedLARS
 against FusedSGD, FusedLAMB against FusedAdam.
 
-    python tools/optim_step_bench.py [--steps 200] [--rounds 5] [--arms sgd,lars,adam,lamb] [--out FILE]
+    python tools/optim_step_bench.py [--steps 200] [--rounds 5] [--arms sgd,lars,adam,lamb] [--clip] [--out FILE]
 
 Every optimizer steps its own copy of the same parameters and gradients (weight decay 1e-4; momentum
 0.9 for SGD / LARS), eagerly and as a replayed HIP graph of one step.  Timing: HIP events around
@@ -13,6 +13,10 @@ once more for the norms (28 B); Adam reads p, g, m, v and writes p, m, v (28 B);
 reads p, g, m, v and writes m, v, its update reads p, m, v and writes p (40 B).  The script prints
 the measured ratios and, beside them, each arm's bytes / time; it makes no statement on where a
 second read is served from.
+
+``--clip`` adds a clipped arm per optimizer (``max_grad_norm=1``, ``skip_nonfinite``; the gradients'
+norm is 5, so every step clips): the norm pass reads g once more (+4 B per element) and one
+workgroup merges the 6,240 chunk sums.  It also times the norm pass and the finish kernel alone.
 """
 import argparse
 import os
@@ -36,6 +40,10 @@ ARMS = {
     "lamb": (FusedLAMB, dict(lr=1e-3, weight_decay=1e-4), 40),
 }
 RATIOS = (("lars", "sgd"), ("lamb", "adam"), ("adam", "sgd"))
+CLIP = dict(max_grad_norm=1.0, skip_nonfinite=True)
+for _k in list(ARMS):
+    ARMS[_k + "+clip"] = (ARMS[_k][0], dict(ARMS[_k][1], **CLIP), ARMS[_k][2] + 4)
+CLIP_RATIOS = tuple((k + "+clip", k) for k in ("sgd", "adam", "lars", "lamb"))
 
 
 def _arm(cls, shapes, dev, seed, **kw):
@@ -62,6 +70,8 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--arms", default="sgd,lars,adam,lamb")
     ap.add_argument("--modes", default="eager,graph")
+    ap.add_argument("--clip", action="store_true", help="add a clipped arm per optimizer, the norm pass and the "
+                                                        "finish kernel alone")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -69,12 +79,15 @@ def main(argv=None):
     _ext.hip_ops()
     dev = torch.device("cuda", 0)
     names = [k for k in a.arms.split(",") if k]
+    if a.clip:
+        names += [k + "+clip" for k in names if "+" not in k]
     shapes = [tuple(p.shape) for p in build_model("resnet50", num_classes=1000).parameters()]
     n = sum(int(torch.Size(s).numel()) for s in shapes)
     lines = [f"# optim_step_bench: {len(shapes)} tensors, {n} elements (ResNet-50), wd 1e-4, "
              f"{a.rounds} alternating blocks of {a.steps} steps, median [min .. max] us per step",
              f"# device: {torch.cuda.get_device_name(0)}"]
-    arms = {k: _arm(ARMS[k][0], shapes, dev, 1, **ARMS[k][1])[1].step for k in names}
+    opts = {k: _arm(ARMS[k][0], shapes, dev, 1, **ARMS[k][1])[1] for k in names}
+    arms = {k: o.step for k, o in opts.items()}
     for f in arms.values():  # first launches, tables, the device learning rate and step counters
         for _ in range(3):
             f()
@@ -109,12 +122,25 @@ def main(argv=None):
             res[(mode, k)] = med
             lines.append(f"{mode:5s} {k:4s} {med:8.1f} us  [{min(t[k]):.1f} .. {max(t[k]):.1f}]   "
                          f"{bytes_per[k] / 1e6:.0f} MB accounted -> {bytes_per[k] / med / 1e6:.2f} TB/s")
-        for num, den in RATIOS:
+        for num, den in RATIOS + CLIP_RATIOS:
             if num in fns and den in fns:
                 ratio = res[(mode, num)] / res[(mode, den)]
                 lines.append(f"{mode:5s} {num.upper()} / {den.upper()} step-time ratio {ratio:.3f}  (traffic model "
                              f"{ARMS[num][2] / ARMS[den][2]:.2f}; extra {res[(mode, num)] - res[(mode, den)]:.1f} us "
                              "per step)")
+    clipped = [k for k in names if k.endswith("+clip")]
+    if clipped:
+        o = opts[clipped[0]]
+        parts = {"norm pass (mt_gnorm2)": (lambda: o.norm_params(None), 4 * n), "finish (gnorm_finish)": (o._finish_norm, 0)}
+        for label, (f, nbytes) in parts.items():
+            _time_block(f, a.steps)
+            t = [_time_block(f, a.steps) for _ in range(a.rounds)]
+            med = statistics.median(t)
+            rate = f"   {nbytes / 1e6:.0f} MB -> {nbytes / med / 1e6:.2f} TB/s" if nbytes else ""
+            lines.append(f"eager {label:24s} {med:8.1f} us  [{min(t):.1f} .. {max(t):.1f}]{rate}")
+        o.step()  # a whole step again: the finish-only blocks above merged no partials of their own epoch
+        lines.append(f"# clipped arms: grad norm {float(o.grad_norm()):.4f}, coefficient {float(o.clip_coef()):.4f}, "
+                     f"skipped {int(o.skipped_steps())}")
     text = "\n".join(lines)
     print(text)
     if a.out:
