@@ -17,6 +17,7 @@ from __future__ import annotations
 import torch.nn as nn
 
 from ..engine.loop import ClassificationLoop
+from ..config import refuse_mix
 from ..engine.runtime import build_data, setup
 from ..models import build_model
 from ..models.heads import ArcMarginProduct, MLPHead
@@ -50,6 +51,7 @@ def build_arcface(args):
 
 
 def run(args):
+    refuse_mix(args, "arcface")
     rt = setup(args)
     train_data, val_data, _, _ = build_data(args, rt)
     model = build_arcface(args).to(rt.device)

@@ -46,10 +46,14 @@ def run(args):
     attach_optimizer(net, opt)  # multi-GPU: the step runs per gradient bucket behind its all-reduce
     sched = StepLR(opt, step_size=args.step_size, gamma=args.gamma)
     C = args.num_classes
+    mixed = getattr(train_data, "mix", None) is not None
 
     def fwd_train(batch):
         x, y = batch[0], batch[1]
-        return Fn.cross_entropy(net(x), y, C, smoothing=args.label_smoothing, return_rank=True)
+        # a Mixup / CutMix loader yields (x, labels, partner, wlab): the two-label loss (the rank it
+        # returns, and so the training top-1 / top-3, is against the row's own label)
+        mix = (batch[2], batch[3]) if mixed else None
+        return Fn.cross_entropy(net(x), y, C, smoothing=args.label_smoothing, return_rank=True, mix=mix)
 
     def fwd_eval(batch):
         x, y = batch[0], batch[1]

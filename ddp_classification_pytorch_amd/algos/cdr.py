@@ -97,6 +97,9 @@ def run(args):
     """CDR/main.py:286-383: ResNet-50 + MLP head + LogSoftmax, SGD(momentum 0.9),
     MultiStepLR([10, 20]) stepped BEFORE each epoch (reference order), CE on the
     log-probabilities, critical-parameter masking after every backward."""
+    from ..config import refuse_mix
+
+    refuse_mix(args, "cdr")
     from ..algos.baseline import build_classifier
     from ..engine.loop import ClassificationLoop
     from ..engine.logger import rotate_results_file

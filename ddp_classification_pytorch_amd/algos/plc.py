@@ -26,6 +26,7 @@ import torch.distributed as dist
 
 from ..engine.logger import MetricsLogger
 from ..engine.loop import ClassificationLoop
+from ..config import refuse_mix
 from ..engine.runtime import build_data, setup
 from ..ops import functional as Fn
 from ..optim import FusedSGD
@@ -152,6 +153,7 @@ def posteriors(model, loader, n, num_classes):
 def run(args):
     """Labels live in a device table indexed by dataset index, so corrections are
     visible immediately (persistent loader workers hold stale dataset copies)."""
+    refuse_mix(args, "plc")
     from .baseline import build_classifier
 
     rt = setup(args)

@@ -132,6 +132,16 @@ def build_parser() -> argparse.ArgumentParser:
     a("--lrSchedule", "--milestones", dest="milestones", type=int, nargs="+", default=None)
     a("--warmup-iters", "--warmUpIter", dest="warmup_iters", type=int, default=0)
     a("--label-smoothing", type=float, default=0.0)
+    # Mixup / CutMix on the device (data/mix.py; the baseline workload only)
+    a("--mixup-alpha", dest="mixup_alpha", type=float, default=0.0,
+      help="Mixup: lam ~ Beta(alpha, alpha) blends each image and label with its partner's (0 = off)")
+    a("--cutmix-alpha", dest="cutmix_alpha", type=float, default=0.0,
+      help="CutMix: a box of area (1 - lam) H W of the partner's image is pasted in (0 = off)")
+    a("--mix-prob", dest="mix_prob", type=float, default=1.0, help="probability that a draw is mixed at all")
+    a("--mix-switch-prob", dest="mix_switch_prob", type=float, default=0.5,
+      help="with both alphas positive: probability of CutMix, else Mixup")
+    a("--mix-mode", dest="mix_mode", default="batch", choices=["batch", "elem"],
+      help="one draw per batch, or one per image")
     # run control / persistence
     a("--seed", type=int, default=999)
     a("--out-dir", "--out_dir", "--result_dir", dest="out_dir", default="output")
@@ -225,6 +235,21 @@ def resolve(args: argparse.Namespace) -> argparse.Namespace:
     if args.nested > 0 and args.dropout > 0:
         raise ValueError("nested dropout and standard dropout are mutually exclusive (NESTED/train.py:489-490)")
     return args
+
+
+def mix_enabled(args) -> bool:
+    """Mixup / CutMix is on when either alpha is positive."""
+    return float(getattr(args, "mixup_alpha", 0) or 0) > 0 or float(getattr(args, "cutmix_alpha", 0) or 0) > 0
+
+
+def refuse_mix(args, workload: str):
+    """The workloads whose heads and losses take one label per row (ArcFace, CDR, nested, PLC) call
+    this at start-up: a mix flag there is an error, never silently ignored."""
+    defaults = dict(mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, mix_switch_prob=0.5, mix_mode="batch")
+    given = [f"--{k.replace('_', '-')}" for k, d in defaults.items() if getattr(args, k, d) != d]
+    if given:
+        raise ValueError(f"{', '.join(given)}: Mixup / CutMix is wired for --workload baseline only; the {workload} "
+                         f"workload's head and loss take one label per image")
 
 
 def _cuda_available() -> bool:

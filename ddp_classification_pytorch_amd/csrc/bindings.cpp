@@ -1608,6 +1608,70 @@ Tensor to_nhwc_s2d(const Tensor& src, bool nchw, double in_scale, const optional
   return y;
 }
 
+// Mixup / CutMix plan of a batch of N images (data/mix.py): all three on the images' device
+static void check_mix_plan(const Tensor& src, int64_t N, int64_t C, const Tensor& partner, const Tensor& blend,
+                           const Tensor& box, const char* op, const optional<Tensor>& mean,
+                           const optional<Tensor>& stdv) {
+  for (const auto* t : {&mean, &stdv})
+    TORCH_CHECK(!t->has_value() || ((*t)->is_cuda() && (*t)->scalar_type() == at::kFloat && (*t)->is_contiguous() &&
+                                    (*t)->numel() >= C),
+                op, ": mean / std are fp32 GPU tensors with an entry per channel");
+  TORCH_CHECK(partner.is_cuda() && blend.is_cuda() && box.is_cuda() && partner.device() == src.device() &&
+                  blend.device() == src.device() && box.device() == src.device(),
+              op, ": the plan lives on the images' device");
+  TORCH_CHECK(partner.scalar_type() == at::kInt && partner.is_contiguous() && partner.numel() == N, op,
+              ": partner int32 [N]");
+  TORCH_CHECK(blend.scalar_type() == at::kFloat && blend.is_contiguous() && blend.numel() == N, op,
+              ": blend fp32 [N]");
+  TORCH_CHECK(box.scalar_type() == at::kInt && box.is_contiguous() && box.numel() == 4 * N, op, ": box int32 [N, 4]");
+}
+
+// to_nhwc with image n mixed with image partner[n] (the 8-slot pixel kernel only)
+Tensor to_nhwc_mix(const Tensor& src, bool nchw, int64_t cpad, double in_scale, const optional<Tensor>& mean,
+                   const optional<Tensor>& stdv, const Tensor& partner, const Tensor& blend, const Tensor& box) {
+  CHECK_DEV(src);
+  CHECK_CONTIG(src);
+  TORCH_CHECK(src.dim() == 4, "to_nhwc_mix: 4-d image batch");
+  TORCH_CHECK(src.scalar_type() == at::kByte || src.scalar_type() == at::kFloat, "to_nhwc_mix input u8 or fp32");
+  const int N = src.size(0);
+  const int C = nchw ? src.size(1) : src.size(3);
+  const int H = nchw ? src.size(2) : src.size(1);
+  const int W = nchw ? src.size(3) : src.size(2);
+  TORCH_CHECK(cpad == 8 && C <= 8, "to_nhwc_mix: only the 8-slot layout (cpad 8, <= 8 channels) has a mixed kernel, got cpad ",
+              cpad, " with ", C, " channels");
+  check_mix_plan(src, N, C, partner, blend, box, "to_nhwc_mix", mean, stdv);
+  auto y = at::empty({N, H, W, 8}, src.options().dtype(at::kBFloat16));
+  const int rc = dcp::launch_to_nhwc_mix(src.data_ptr(), src.scalar_type() == at::kByte, nchw, N, C, H, W,
+                                         (float)in_scale, fp(mean), fp(stdv), partner.data_ptr<int>(),
+                                         blend.data_ptr<float>(), box.data_ptr<int>(), bpm(y), cur_stream(), 0);
+  TORCH_CHECK(rc == 0, "to_nhwc_mix: the output pixels exceed the 32-bit index range");
+  return y;
+}
+
+Tensor to_nhwc_s2d_mix(const Tensor& src, bool nchw, double in_scale, const optional<Tensor>& mean,
+                       const optional<Tensor>& stdv, const Tensor& partner, const Tensor& blend, const Tensor& box,
+                       int64_t block) {
+  CHECK_DEV(src);
+  CHECK_CONTIG(src);
+  TORCH_CHECK(src.dim() == 4, "to_nhwc_s2d_mix: 4-d image batch");
+  TORCH_CHECK(src.scalar_type() == at::kByte || src.scalar_type() == at::kFloat, "to_nhwc_s2d_mix input u8 or fp32");
+  const int N = src.size(0);
+  const int C = nchw ? src.size(1) : src.size(3);
+  const int H = nchw ? src.size(2) : src.size(1);
+  const int W = nchw ? src.size(3) : src.size(2);
+  TORCH_CHECK(block == 2 || block == 4, "to_nhwc_s2d_mix block is 2 or 4");
+  const int b = (int)block, cq = b == 2 ? 4 : 3;
+  TORCH_CHECK(C <= cq && H % b == 0 && W % b == 0, "to_nhwc_s2d_mix needs <= ", cq, " channels and H, W divisible by ",
+              b);
+  check_mix_plan(src, N, C, partner, blend, box, "to_nhwc_s2d_mix", mean, stdv);
+  auto y = at::empty({N, H / b, W / b, b * b * cq}, src.options().dtype(at::kBFloat16));
+  const int rc = dcp::launch_to_nhwc_mix(src.data_ptr(), src.scalar_type() == at::kByte, nchw, N, C, H, W,
+                                         (float)in_scale, fp(mean), fp(stdv), partner.data_ptr<int>(),
+                                         blend.data_ptr<float>(), box.data_ptr<int>(), bpm(y), cur_stream(), b);
+  TORCH_CHECK(rc == 0, "to_nhwc_s2d_mix: the output pixels exceed the 32-bit index range");
+  return y;
+}
+
 Tensor act_bwd(const Tensor& dy, const Tensor& y, int64_t act) {
   CHECK_ACT(dy);
   CHECK_ACT(y);
@@ -1832,6 +1896,49 @@ Tensor xent_bwd(const Tensor& logits, const Tensor& labels, int64_t C, const Ten
   dcp::launch_xent_bwd(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, B, ld, C,
                        labels.data_ptr<int64_t>(), g.data_ptr<float>(), (float)scale, (float)smoothing, d.data_ptr(),
                        ldo, out_bf16, cur_stream());
+  return d;
+}
+
+// the label pair of a mixed batch (data/mix.py): partner int32 [B], wlab fp32 [B], on the logits' device
+static void check_label_plan(const Tensor& logits, const Tensor& labels, const Tensor& partner, const Tensor& wlab,
+                             int64_t C) {
+  CHECK_DEV(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits rows must be contiguous");
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits bf16 or fp32");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda() && labels.is_contiguous() && labels.numel() == B,
+              "labels int64 [B] on GPU");
+  TORCH_CHECK(partner.scalar_type() == at::kInt && partner.is_cuda() && partner.is_contiguous() &&
+                  partner.numel() == B,
+              "partner int32 [B] on GPU");
+  TORCH_CHECK(wlab.scalar_type() == at::kFloat && wlab.is_cuda() && wlab.is_contiguous() && wlab.numel() == B,
+              "wlab fp32 [B] on GPU");
+  TORCH_CHECK(C >= 1 && C <= logits.size(1) && C <= logits.stride(0), "xent_mix shapes");
+}
+
+// -> (loss_rows, rank); rank is the rank of the row's OWN label labels[b]
+std::tuple<Tensor, Tensor> xent_mix_fwd(const Tensor& logits, const Tensor& labels, const Tensor& partner,
+                                        const Tensor& wlab, int64_t C, double smoothing) {
+  check_label_plan(logits, labels, partner, wlab, C);
+  const int B = logits.size(0), ld = logits.stride(0);
+  auto loss = at::empty({B}, f32_like(logits));
+  auto rank = at::empty({B}, logits.options().dtype(at::kInt));
+  dcp::launch_xent_mix_fwd(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, B, ld, C,
+                           labels.data_ptr<int64_t>(), partner.data_ptr<int>(), wlab.data_ptr<float>(),
+                           loss.data_ptr<float>(), rank.data_ptr<int>(), (float)smoothing, cur_stream());
+  return {loss, rank};
+}
+
+Tensor xent_mix_bwd(const Tensor& logits, const Tensor& labels, const Tensor& partner, const Tensor& wlab, int64_t C,
+                    const Tensor& grad_out, double scale, double smoothing, bool out_bf16) {
+  check_label_plan(logits, labels, partner, wlab, C);
+  const int B = logits.size(0), ld = logits.stride(0), ldo = logits.size(1);
+  auto d = at::empty({B, ldo}, logits.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+  auto g = grad_out.to(at::kFloat).contiguous();
+  dcp::launch_xent_mix_bwd(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, B, ld, C,
+                           labels.data_ptr<int64_t>(), partner.data_ptr<int>(), wlab.data_ptr<float>(),
+                           g.data_ptr<float>(), (float)scale, (float)smoothing, d.data_ptr(), ldo, out_bf16,
+                           cur_stream());
   return d;
 }
 
@@ -2367,6 +2474,12 @@ TORCH_LIBRARY(dcp, m) {
   m.def("rotate_nearest_crop(Tensor canvas, Tensor meta, Tensor geo, int Ho, int Wo) -> Tensor",
         &rotate_nearest_crop);
   m.def("to_nhwc_s2d(Tensor src, bool nchw, float in_scale, Tensor? mean, Tensor? std, int block=2) -> Tensor", &to_nhwc_s2d);
+  m.def("to_nhwc_mix(Tensor src, bool nchw, int cpad, float in_scale, Tensor? mean, Tensor? std, Tensor partner, "
+        "Tensor blend, Tensor box) -> Tensor",
+        &to_nhwc_mix);
+  m.def("to_nhwc_s2d_mix(Tensor src, bool nchw, float in_scale, Tensor? mean, Tensor? std, Tensor partner, "
+        "Tensor blend, Tensor box, int block=2) -> Tensor",
+        &to_nhwc_s2d_mix);
   m.def("conv_fwd_geo(Tensor x, Tensor w, int stride, int pad, int Ho, int Wo, bool stats) -> (Tensor, Tensor)",
         &conv_fwd_geo);
   m.def("stem_fwd(Tensor x, Tensor w, bool stats) -> (Tensor, Tensor)", &stem_fwd);
@@ -2403,6 +2516,12 @@ TORCH_LIBRARY(dcp, m) {
       "xent_bwd(Tensor logits, Tensor labels, int C, Tensor grad_out, float scale, float smoothing, bool out_bf16) "
       "-> Tensor",
       &xent_bwd);
+  m.def("xent_mix_fwd(Tensor logits, Tensor labels, Tensor partner, Tensor wlab, int C, float smoothing) -> (Tensor, "
+        "Tensor)",
+        &xent_mix_fwd);
+  m.def("xent_mix_bwd(Tensor logits, Tensor labels, Tensor partner, Tensor wlab, int C, Tensor grad_out, float scale, "
+        "float smoothing, bool out_bf16) -> Tensor",
+        &xent_mix_bwd);
   m.def("log_softmax_fwd(Tensor x, int C) -> Tensor", &log_softmax_fwd);
   m.def("log_softmax_bwd(Tensor y, Tensor dy, int ldo, bool out_bf16) -> Tensor", &log_softmax_bwd);
   m.def("s2d_weight(Tensor w7, Tensor(a!) w16) -> ()", &s2d_weight);

@@ -267,6 +267,14 @@ void launch_metric_accum(double* acc, const float* loss, int nloss, float loss_s
 void launch_xent_bwd(const void* logits, bool in_bf16, int B, int ld, int C, const int64_t* labels,
                      const float* grad_out, float scale, float smoothing, void* dlogits, int ldo, bool out_bf16,
                      hipStream_t s);
+// two-label (Mixup / CutMix) cross-entropy: row b carries labels[b] with weight wlab[b] and
+// labels[partner[b]] with 1 - wlab[b]; rank is that of labels[b]
+void launch_xent_mix_fwd(const void* logits, bool is_bf16, int B, int ld, int C, const int64_t* labels,
+                         const int* partner, const float* wlab, float* loss, int* rank, float smoothing,
+                         hipStream_t s);
+void launch_xent_mix_bwd(const void* logits, bool in_bf16, int B, int ld, int C, const int64_t* labels,
+                         const int* partner, const float* wlab, const float* grad_out, float scale, float smoothing,
+                         void* dlogits, int ldo, bool out_bf16, hipStream_t s);
 void launch_log_softmax_fwd(const void* x, bool is_bf16, int B, int ld, int C, float* y, hipStream_t s);
 void launch_log_softmax_bwd(const float* y, const float* dy, int B, int C, int ldo, void* dx, bool out_bf16,
                             hipStream_t s);
@@ -392,6 +400,12 @@ void launch_to_nhwc(const void* src, int is_u8, int nchw, int N, int C, int H, i
 // real); block 4 (TResNet SpaceToDepth(4)) dst [N][H/4][W/4][48], channel (py*4+px)*3 + c
 void launch_to_nhwc_s2d(const void* src, int is_u8, int nchw, int N, int C, int H, int W, float in_scale,
                         const float* mean, const float* stdv, bf16* dst, hipStream_t s, int block = 2);
+// Mixup / CutMix while normalising: row n mixed with row partner[n] by blend[n] outside box[n] = {y0, x0, y1, x1}
+// and replaced by it inside (misc.hip).  block 0: the plain [N][H][W][8] layout; 2 / 4: as launch_to_nhwc_s2d.
+// Returns 1 (nothing launched) when the output pixels exceed the 32-bit index range.
+int launch_to_nhwc_mix(const void* src, int is_u8, int nchw, int N, int C, int H, int W, float in_scale,
+                       const float* mean, const float* stdv, const int* partner, const float* blend, const int* box,
+                       bf16* dst, hipStream_t s, int block);
 // shard-loader augmentation: meta [B][8] = {byte offset, H, W, y0, x0, h, w, flip} -> out [B][Ho][Wo][3]
 void launch_crop_resize(const uint8_t* src, const int64_t* meta, int B, int Ho, int Wo, uint8_t* out, hipStream_t s);
 // the same with a per-image inverse affine map xf [B][8] = {m00, m01, m02, m10, m11, m12, angle_deg, 0}

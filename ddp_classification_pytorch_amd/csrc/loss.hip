@@ -83,6 +83,91 @@ __global__ void __launch_bounds__(256) xent_bwd_kernel(const T* __restrict__ log
   }
 }
 
+// Two-label cross-entropy (Mixup / CutMix, data/mix.py): row b carries its own label a = labels[b]
+// with weight w = wlab[b] and its partner's, b2 = labels[partner[b]] (read here: no gather launch),
+// with 1 - w.  One workgroup per row, the passes of xent_fwd_kernel:
+//   la = lse - x_a;  lb = lse - x_b2;  loss = fmaf(w, la, (1 - w) * lb)   (+ smoothing as above)
+// rank[b] = #{j : x_j > x_a}: the rank of the row's OWN label.  A row is valid only if both labels
+// are in [0, C); otherwise its loss (and its gradient row below) is 0.  partner is clamped to [0, B).
+template <typename T>
+__global__ void __launch_bounds__(256) xent_mix_fwd_kernel(const T* __restrict__ logits, int ld, int C, int B,
+                                                           const int64_t* __restrict__ labels,
+                                                           const int* __restrict__ partner,
+                                                           const float* __restrict__ wlab, float* __restrict__ loss,
+                                                           int* __restrict__ rank, float smoothing) {
+  __shared__ float red[16];
+  const int b = blockIdx.x;
+  const T* row = logits + (size_t)b * ld;
+  const int la_ = (int)labels[b];
+  const int lb_ = (int)labels[min(max(partner[b], 0), B - 1)];
+  const bool va = la_ >= 0 && la_ < C, vb = lb_ >= 0 && lb_ < C;
+  const float xl = va ? ldf(row + la_) : 0.f;
+  const float xb = vb ? ldf(row + lb_) : 0.f;
+  float mx = -INFINITY;
+  int cnt = 0;
+  for (int j = threadIdx.x; j < C; j += blockDim.x) {
+    const float v = ldf(row + j);
+    mx = fmaxf(mx, v);
+    cnt += v > xl;
+  }
+  mx = block_max(mx, red);
+  float se = 0.f, sx = 0.f;
+  for (int j = threadIdx.x; j < C; j += blockDim.x) {
+    const float v = ldf(row + j);
+    se += __expf(v - mx);
+    sx += v;
+  }
+  se = block_sum(se, red);
+  sx = block_sum(sx, red);
+  const float c = block_sum((float)cnt, red);
+  if (threadIdx.x == 0) {
+    const float lse = mx + __logf(se);
+    const float w = wlab[b];
+    const float la = lse - xl, lb = lse - xb;
+    float l = fmaf(w, la, (1.f - w) * lb);
+    if (smoothing > 0.f) l = (1.f - smoothing) * l + smoothing * (lse - sx / C);
+    loss[b] = (va && vb) ? l : 0.f;
+    if (rank) rank[b] = (int)c;
+  }
+}
+
+// dlogits_j = g * (p_j - t_j),  t_j = (1 - s) * (w [j == a] + (1 - w) [j == b2]) + s / C ; pad columns -> 0
+template <typename T, typename TO>
+__global__ void __launch_bounds__(256) xent_mix_bwd_kernel(const T* __restrict__ logits, int ld, int C, int B,
+                                                           const int64_t* __restrict__ labels,
+                                                           const int* __restrict__ partner,
+                                                           const float* __restrict__ wlab,
+                                                           const float* __restrict__ grad_out, float scale,
+                                                           float smoothing, TO* __restrict__ dlogits, int ldo) {
+  __shared__ float red[16];
+  const int b = blockIdx.x;
+  const T* row = logits + (size_t)b * ld;
+  const int la_ = (int)labels[b];
+  const int lb_ = (int)labels[min(max(partner[b], 0), B - 1)];
+  const float w = wlab[b];
+  const float cw = 1.f - w;
+  float mx = -INFINITY;
+  for (int j = threadIdx.x; j < C; j += blockDim.x) mx = fmaxf(mx, ldf(row + j));
+  mx = block_max(mx, red);
+  float se = 0.f;
+  for (int j = threadIdx.x; j < C; j += blockDim.x) se += __expf(ldf(row + j) - mx);
+  se = block_sum(se, red);
+  const float inv = 1.f / se;
+  const bool valid = la_ >= 0 && la_ < C && lb_ >= 0 && lb_ < C;
+  const float g = valid ? grad_out[0] * scale : 0.f;
+  TO* drow = dlogits + (size_t)b * ldo;
+  for (int j = threadIdx.x; j < ldo; j += blockDim.x) {
+    float d = 0.f;
+    if (j < C) {
+      const float pj = __expf(ldf(row + j) - mx) * inv;
+      const float hot = fmaf(w, j == la_ ? 1.f : 0.f, cw * (j == lb_ ? 1.f : 0.f));
+      const float tgt = (1.f - smoothing) * hot + smoothing / C;
+      d = g * (pj - tgt);
+    }
+    drow[j] = (TO)d;
+  }
+}
+
 // log-softmax fwd (fp32 out) and bwd: dx = dy - softmax * sum(dy)
 template <typename T>
 __global__ void __launch_bounds__(256) log_softmax_fwd_kernel(const T* __restrict__ x, int ld, int C,
@@ -282,6 +367,36 @@ void launch_xent_bwd(const void* logits, bool in_bf16, int B, int ld, int C, con
   else
     hipLaunchKernelGGL((xent_bwd_kernel<float, float>), dim3(B), dim3(256), 0, s, (const float*)logits, ld, C,
                        labels, grad_out, scale, smoothing, (float*)dlogits, ldo);
+}
+
+void launch_xent_mix_fwd(const void* logits, bool is_bf16, int B, int ld, int C, const int64_t* labels,
+                         const int* partner, const float* wlab, float* loss, int* rank, float smoothing,
+                         hipStream_t s) {
+  if (B <= 0) return;
+  if (is_bf16)
+    hipLaunchKernelGGL(xent_mix_fwd_kernel<bf16>, dim3(B), dim3(256), 0, s, (const bf16*)logits, ld, C, B, labels,
+                       partner, wlab, loss, rank, smoothing);
+  else
+    hipLaunchKernelGGL(xent_mix_fwd_kernel<float>, dim3(B), dim3(256), 0, s, (const float*)logits, ld, C, B, labels,
+                       partner, wlab, loss, rank, smoothing);
+}
+
+void launch_xent_mix_bwd(const void* logits, bool in_bf16, int B, int ld, int C, const int64_t* labels,
+                         const int* partner, const float* wlab, const float* grad_out, float scale, float smoothing,
+                         void* dlogits, int ldo, bool out_bf16, hipStream_t s) {
+  if (B <= 0) return;
+  if (in_bf16 && out_bf16)
+    hipLaunchKernelGGL((xent_mix_bwd_kernel<bf16, bf16>), dim3(B), dim3(256), 0, s, (const bf16*)logits, ld, C, B,
+                       labels, partner, wlab, grad_out, scale, smoothing, (bf16*)dlogits, ldo);
+  else if (in_bf16)
+    hipLaunchKernelGGL((xent_mix_bwd_kernel<bf16, float>), dim3(B), dim3(256), 0, s, (const bf16*)logits, ld, C, B,
+                       labels, partner, wlab, grad_out, scale, smoothing, (float*)dlogits, ldo);
+  else if (out_bf16)
+    hipLaunchKernelGGL((xent_mix_bwd_kernel<float, bf16>), dim3(B), dim3(256), 0, s, (const float*)logits, ld, C, B,
+                       labels, partner, wlab, grad_out, scale, smoothing, (bf16*)dlogits, ldo);
+  else
+    hipLaunchKernelGGL((xent_mix_bwd_kernel<float, float>), dim3(B), dim3(256), 0, s, (const float*)logits, ld, C, B,
+                       labels, partner, wlab, grad_out, scale, smoothing, (float*)dlogits, ldo);
 }
 
 void launch_log_softmax_fwd(const void* x, bool is_bf16, int B, int ld, int C, float* y, hipStream_t s) {

@@ -452,6 +452,119 @@ __global__ void __launch_bounds__(256) to_nhwc_pix_kernel(const void* __restrict
   }
 }
 
+// The mixed form of to_nhwc_pix_kernel (Mixup / CutMix, data/mix.py): image n is mixed with image
+// partner[n] of the same batch while it is normalised.  With na / nb the values the kernel above
+// WRITES for the row's own and for the partner's source pixel (same expression, rounded to bf16 as
+// there: the bits of the unmixed output):
+//   inside box[n] = {y0, x0, y1, x1} (source pixels, half open):  v = nb
+//   elsewhere:                                                    v = fmaf(blend, na, (1 - blend) * nb)
+// and dst = f2bf(v): the blend of the two unmixed bf16 images, formed in fp32 and rounded once, so it
+// is within one bf16 rounding of blend * A + (1 - blend) * B for the unmixed outputs A, B (blending
+// the unrounded fp32 values instead would sit up to three roundings from that).  The decision is per SOURCE pixel: a 2x2 / 4x4 output block may straddle a
+// box edge.  The plan of a row is read once per output pixel (uniform over a wave except where the
+// wave spans two images).  A row with blend == 1 reads one image per pixel -- its partner inside the
+// box, itself elsewhere, so the identity plan never touches a partner and costs the bytes of the
+// unmixed kernel -- and takes na outside the box as it is (fmaf(1, na, 0 * nb) for every finite nb).
+// partner is clamped into [0, N) and the box into the image, so no plan can address outside the batch.
+template <int S, int CQ>
+__global__ void __launch_bounds__(256) to_nhwc_pix_mix_kernel(const void* __restrict__ src, int is_u8, int nchw,
+                                                              int N, int C, int H, int W, float in_scale,
+                                                              const float* __restrict__ mean,
+                                                              const float* __restrict__ stdv,
+                                                              const int* __restrict__ partner,
+                                                              const float* __restrict__ blend,
+                                                              const int* __restrict__ box, bf16* __restrict__ dst) {
+  constexpr int OC = S * S * CQ;
+  const int Ho = H / S, Wo = W / S;
+  const size_t total = (size_t)N * Ho * Wo;
+  float mu[CQ], is[CQ];
+#pragma unroll
+  for (int c = 0; c < CQ; ++c) {
+    mu[c] = (c < C && mean) ? mean[c] : 0.f;
+    is[c] = (c < C && stdv) ? 1.f / stdv[c] : 1.f;
+  }
+  for (uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x; pix < (uint32_t)total; pix += gridDim.x * blockDim.x) {
+    const int j = (int)(pix % (uint32_t)Wo);
+    const uint32_t q = pix / (uint32_t)Wo;
+    const int i = (int)(q % (uint32_t)Ho);
+    const uint32_t ni = q / (uint32_t)Ho;
+    const size_t n = ni;
+    const size_t m = (size_t)min(max(partner[ni], 0), N - 1);
+    const float bl = blend[ni];
+    const float cb = 1.f - bl;
+    const int by0 = min(max(box[4 * ni + 0], 0), H), bx0 = min(max(box[4 * ni + 1], 0), W);
+    const int by1 = min(max(box[4 * ni + 2], 0), H), bx1 = min(max(box[4 * ni + 3], 0), W);
+    const bool boxed = by1 > by0 && bx1 > bx0;
+    const bool blended = bl != 1.f;
+    bf16 o[OC];
+    // Every pixel loads its first operand unconditionally, as the unmixed kernel does, from the image
+    // it comes from (the partner inside the box, the row's own elsewhere); only a blending row
+    // (uniform per image) loads the partner's pixel as a second operand.
+    if (S == 2 && is_u8 && nchw && (W & 1) == 0) {
+      // the packed two-byte load of the unmixed kernel; a pair that straddles a box edge loads twice
+#pragma unroll
+      for (int py = 0; py < S; ++py) {
+        const int y = i * S + py, x = j * S;
+        const bool iny = boxed && y >= by0 && y < by1;
+        const bool in0 = iny && x >= bx0 && x < bx1, in1 = iny && x + 1 >= bx0 && x + 1 < bx1;
+        const size_t f0 = in0 ? m : n, f1 = in1 ? m : n;
+#pragma unroll
+        for (int c = 0; c < CQ; ++c) {
+          float v0 = 0.f, v1 = 0.f;
+          if (c < C) {
+            const size_t off = ((size_t)c * H + (size_t)y) * W + (size_t)x;
+            const size_t img = (size_t)C * H * W;
+            const uint16_t t0 = *(const uint16_t*)((const uint8_t*)src + f0 * img + off);
+            const uint16_t t1 = f1 == f0 ? t0 : *(const uint16_t*)((const uint8_t*)src + f1 * img + off);
+            v0 = ((float)(t0 & 0xff) * in_scale - mu[c]) * is[c];
+            v1 = ((float)(t1 >> 8) * in_scale - mu[c]) * is[c];
+            if (blended) {
+              const uint16_t tb = *(const uint16_t*)((const uint8_t*)src + m * img + off);
+              const float nb0 = ((float)(tb & 0xff) * in_scale - mu[c]) * is[c];
+              const float nb1 = ((float)(tb >> 8) * in_scale - mu[c]) * is[c];
+              v0 = in0 ? nb0 : fmaf(bl, bf2f(f2bf(v0)), cb * bf2f(f2bf(nb0)));
+              v1 = in1 ? nb1 : fmaf(bl, bf2f(f2bf(v1)), cb * bf2f(f2bf(nb1)));
+            }
+          }
+          o[(py * S + 0) * CQ + c] = f2bf(v0);
+          o[(py * S + 1) * CQ + c] = f2bf(v1);
+        }
+      }
+    } else
+#pragma unroll
+    for (int py = 0; py < S; ++py)
+#pragma unroll
+      for (int px = 0; px < S; ++px) {
+        const size_t y = (size_t)i * S + py, x = (size_t)j * S + px;
+        const bool in = boxed && (int)y >= by0 && (int)y < by1 && (int)x >= bx0 && (int)x < bx1;
+        const size_t f = in ? m : n;
+#pragma unroll
+        for (int c = 0; c < CQ; ++c) {
+          float v = 0.f;
+          if (c < C) {
+            const size_t si = nchw ? ((f * C + c) * H + y) * W + x : ((f * H + y) * W + x) * C + c;
+            const float raw = is_u8 ? (float)((const uint8_t*)src)[si] : ((const float*)src)[si];
+            v = (raw * in_scale - mu[c]) * is[c];
+            if (blended) {
+              const size_t sb = nchw ? ((m * C + c) * H + y) * W + x : ((m * H + y) * W + x) * C + c;
+              const float rawb = is_u8 ? (float)((const uint8_t*)src)[sb] : ((const float*)src)[sb];
+              const float nb = (rawb * in_scale - mu[c]) * is[c];
+              v = in ? nb : fmaf(bl, bf2f(f2bf(v)), cb * bf2f(f2bf(nb)));
+            }
+          }
+          o[(py * S + px) * CQ + c] = f2bf(v);
+        }
+      }
+#pragma unroll
+    for (int k = 0; k < OC / 8; ++k) {
+      bf16x8 w;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) w[e] = o[k * 8 + e];
+      *(bf16x8*)(dst + (size_t)pix * OC + k * 8) = w;
+    }
+  }
+}
+
 // block 2: [N][H/2][W/2][16] (2x2, 4 channel slots: the ResNet s2d stem); block 4:
 // [N][H/4][W/4][48] (4x4, 3 channels: TResNet's SpaceToDepth(4) stem, written straight from the
 // images instead of an NHWC pass plus a space_to_depth pass)
@@ -491,6 +604,29 @@ void launch_to_nhwc(const void* src, int is_u8, int nchw, int N, int C, int H, i
   if (g > 8192) g = 8192;
   hipLaunchKernelGGL(to_nhwc_kernel, dim3((int)g), dim3(256), 0, s, src, is_u8, nchw, N, C, H, W, Cp, in_scale, mean,
                      stdv, dst);
+}
+
+// The mixed input kernels: block 0 the plain 8-slot NHWC layout, 2 / 4 the space-to-depth stems.
+// Returns 0, or 1 when the output pixels exceed the 32-bit index range (nothing is launched).
+int launch_to_nhwc_mix(const void* src, int is_u8, int nchw, int N, int C, int H, int W, float in_scale,
+                       const float* mean, const float* stdv, const int* partner, const float* blend, const int* box,
+                       bf16* dst, hipStream_t s, int block) {
+  const int b = block ? block : 1;
+  size_t total = (size_t)N * (H / b) * (W / b);
+  if (total >= (1ull << 31)) return 1;
+  if (total == 0) return 0;
+  size_t g = (total + 255) / 256;
+  if (g > (1u << 20)) g = 1u << 20;
+  if (block == 4)
+    hipLaunchKernelGGL((to_nhwc_pix_mix_kernel<4, 3>), dim3((int)g), dim3(256), 0, s, src, is_u8, nchw, N, C, H, W,
+                       in_scale, mean, stdv, partner, blend, box, dst);
+  else if (block == 2)
+    hipLaunchKernelGGL((to_nhwc_pix_mix_kernel<2, 4>), dim3((int)g), dim3(256), 0, s, src, is_u8, nchw, N, C, H, W,
+                       in_scale, mean, stdv, partner, blend, box, dst);
+  else
+    hipLaunchKernelGGL((to_nhwc_pix_mix_kernel<1, 8>), dim3((int)g), dim3(256), 0, s, src, is_u8, nchw, N, C, H, W,
+                       in_scale, mean, stdv, partner, blend, box, dst);
+  return 0;
 }
 
 void launch_act_bwd(const bf16* dy, const bf16* y, bf16* dx, size_t numel, int act, hipStream_t s) {

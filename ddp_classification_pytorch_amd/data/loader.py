@@ -43,10 +43,15 @@ def build_loader(dataset, batch_size, sampler=None, shuffle=False, workers=4, dr
 
 class DevicePrefetcher:
     """Wraps a loader of (uint8 HWC images, labels[, index]) and yields
-    (NHWC activations, labels[, index]) on ``device``."""
+    (NHWC activations, labels[, index]) on ``device``.
 
-    def __init__(self, loader, device, mean=IMAGENET_MEAN, std=IMAGENET_STD, cpad=8, s2d=False):
+    ``mix`` (a :class:`~.mix.MixSampler`; train loaders only): the batch is mixed by the input
+    kernel and the tuple becomes (activations, labels, partner, wlab[, index]) -- the identity plan
+    on an unmixed step, so its shapes never change."""
+
+    def __init__(self, loader, device, mean=IMAGENET_MEAN, std=IMAGENET_STD, cpad=8, s2d=False, mix=None):
         self.loader, self.device, self.cpad, self.s2d = loader, torch.device(device), cpad, s2d
+        self.mix = mix
         self.mean = torch.tensor(mean, dtype=torch.float32, device=self.device)
         self.std = torch.tensor(std, dtype=torch.float32, device=self.device)
         self.cuda = self.device.type == "cuda"
@@ -59,25 +64,35 @@ class DevicePrefetcher:
     def sampler(self):
         return getattr(self.loader, "sampler", None)
 
-    def _convert(self, batch):
+    def _convert(self, batch, step=0):
         imgs, labels = batch[0], batch[1]
         imgs = imgs.to(self.device, non_blocking=True)
         labels = labels.to(self.device, non_blocking=True)
+        plan = None
+        if self.mix is not None:
+            plan = self.mix.device_plan(imgs.shape[0], imgs.shape[1], imgs.shape[2], step, self.device)
         x = Fn.to_device_nhwc(imgs, self.mean, self.std, cpad=self.cpad, nchw=False, in_scale=1.0 / 255.0,
-                              s2d=Fn.s2d_for(self.s2d, imgs.shape[1], imgs.shape[2]))
+                              s2d=Fn.s2d_for(self.s2d, imgs.shape[1], imgs.shape[2]), mix=plan)
         rest = tuple(b.to(self.device, non_blocking=True) for b in batch[2:])
+        if plan is not None:
+            return (x, labels, plan.partner, plan.wlab) + rest
         return (x, labels) + rest
 
     def __iter__(self):
-        it = iter(self.loader)
+        it = iter(enumerate(self.loader))
+
+        def convert_next():
+            step, batch = next(it)
+            return self._convert(batch, step)
+
         if not self.cuda:
-            for b in it:
-                yield self._convert(b)
+            for i, b in it:
+                yield self._convert(b, i)
             return
         nxt = None
         try:
             with torch.cuda.stream(self.stream):
-                nxt = self._convert(next(it))
+                nxt = convert_next()
         except StopIteration:
             return
         while nxt is not None:
@@ -87,7 +102,7 @@ class DevicePrefetcher:
                 t.record_stream(torch.cuda.current_stream(self.device))
             try:
                 with torch.cuda.stream(self.stream):
-                    nxt = self._convert(next(it))
+                    nxt = convert_next()
             except StopIteration:
                 nxt = None
             yield cur
@@ -97,8 +112,9 @@ class SyntheticLoader:
     """``steps`` batches of on-device random uint8 images (cycling over ``pool`` distinct batches)."""
 
     def __init__(self, batch_size, steps, size=224, num_classes=1000, device="cuda", pool=2, seed=0,
-                 mean=IMAGENET_MEAN, std=IMAGENET_STD, cpad=8, return_index=False, s2d=False):
+                 mean=IMAGENET_MEAN, std=IMAGENET_STD, cpad=8, return_index=False, s2d=False, mix=None):
         self.device = torch.device(device)
+        self.mix, self.size = mix, size  # mix: a MixSampler -> (x, labels, partner, wlab[, index])
         self.steps, self.cpad, self.return_index, self.batch_size = steps, cpad, return_index, batch_size
         self.s2d = Fn.s2d_for(s2d, size, size)
         g = torch.Generator(device="cpu")
@@ -116,10 +132,12 @@ class SyntheticLoader:
     def __iter__(self):
         for i in range(self.steps):
             k = i % len(self.imgs)
+            plan = None
+            if self.mix is not None:
+                plan = self.mix.device_plan(self.batch_size, self.size, self.size, i, self.device)
             x = Fn.to_device_nhwc(self.imgs[k], self.mean, self.std, cpad=self.cpad, nchw=False, in_scale=1 / 255.0,
-                                  s2d=self.s2d)
+                                  s2d=self.s2d, mix=plan)
+            out = (x, self.labels[k]) if plan is None else (x, self.labels[k], plan.partner, plan.wlab)
             if self.return_index:
-                idx = torch.arange(k * self.batch_size, (k + 1) * self.batch_size, device=self.device)
-                yield x, self.labels[k], idx
-            else:
-                yield x, self.labels[k]
+                out = out + (torch.arange(k * self.batch_size, (k + 1) * self.batch_size, device=self.device),)
+            yield out

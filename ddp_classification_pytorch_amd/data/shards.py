@@ -373,7 +373,8 @@ class ShardLoader:
     def __init__(self, path: str, batch_size: int, sampler=None, aug: AugSpec = None, out_size: int = 224,
                  device="cuda", threads: int = 8, prefetch: int = 3, seed: int = 0, drop_last: bool = False,
                  mean=IMAGENET_MEAN, std=IMAGENET_STD, cpad: int = 8, s2d=False, return_index: bool = False,
-                 resample: str = "fast"):
+                 resample: str = "fast", mix=None):
+        self.mix = mix  # a data.mix.MixSampler (train loaders only)
         if resample not in RESAMPLE_MODES:
             raise ValueError(f"shard resampling mode {resample!r}: one of {RESAMPLE_MODES}")
         self.gather = NativeGather(path, threads)
@@ -454,9 +455,14 @@ class ShardLoader:
             imgs = Fn.crop_resize(src, meta, self.out_size, self.out_size)
         if self.tap is not None:
             self.tap(imgs, meta, extra)
+        plan = None
+        if self.mix is not None:
+            # Mixup / CutMix on the final uint8 batch, after crop / warp / resample (tap saw it unmixed)
+            epoch = getattr(self.sampler, "epoch", self.epoch)
+            plan = self.mix.device_plan(B, self.out_size, self.out_size, slot["step"], self.device, epoch=epoch)
         x = Fn.to_device_nhwc(imgs, self.mean, self.std, cpad=self.cpad, nchw=False, in_scale=1.0 / 255.0,
-                              s2d=self.s2d)
-        out = (x, labels)
+                              s2d=self.s2d, mix=plan)
+        out = (x, labels) if plan is None else (x, labels, plan.partner, plan.wlab)
         if self.return_index:
             out = out + (idx.to(self.device, non_blocking=True),)
         if self.cuda:
@@ -467,17 +473,18 @@ class ShardLoader:
         return out
 
     def __iter__(self):
-        batches = self._batches()
+        batches = enumerate(self._batches())
         inflight = deque()
         free = deque(self.slots)
 
         def fill():
             while free and len(inflight) < self.prefetch:
                 try:
-                    idx = next(batches)
+                    step, idx = next(batches)
                 except StopIteration:
                     return
                 s = free.popleft()
+                s["step"] = step  # the batch's position in the epoch: the mix plan is a function of it
                 self._submit(s, idx)
                 inflight.append(s)
 

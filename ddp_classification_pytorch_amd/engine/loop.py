@@ -203,6 +203,9 @@ class ClassificationLoop:
         sampler = getattr(self.train_data, "sampler", None)
         if sampler is not None and hasattr(sampler, "set_epoch"):
             sampler.set_epoch(epoch)
+        mix = getattr(self.train_data, "mix", None)
+        if mix is not None:
+            mix.set_epoch(epoch)  # Mixup / CutMix plans: a function of (seed, epoch, step, rank)
         acc = torch.zeros(4, dtype=torch.float64, device=dev)  # loss*B, top1, top3, count
         win = torch.zeros(4, dtype=torch.float64, device=dev)
         n_steps = len(self.train_data)

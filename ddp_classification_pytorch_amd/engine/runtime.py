@@ -109,6 +109,19 @@ class WithIndex(torch.utils.data.Dataset):
         return getattr(self.ds, name)
 
 
+def _mix_sampler(args, rt):
+    """--mixup-alpha / --cutmix-alpha: the train loader's Mixup / CutMix plan sampler (data/mix.py),
+    keyed by (seed, rank); None when both alphas are 0."""
+    from ..config import mix_enabled
+
+    if not mix_enabled(args):
+        return None
+    from ..data.mix import MixSampler
+
+    return MixSampler(args.mixup_alpha, args.cutmix_alpha, prob=args.mix_prob, switch_prob=args.mix_switch_prob,
+                      mode=args.mix_mode, seed=args.seed, rank=rt.rank)
+
+
 def _shard_loaders(args, rt, tr, va, tr_s, va_s, mean, std, cpad, s2d, drop_last_train):
     """Native loaders (C++ gather + GPU crop/resize, or the affine warp for the presets that rotate,
     pad or stretch: CDR, CIFAR, PLC).  None -- the PIL DataLoader over the same shard -- only for a
@@ -126,7 +139,7 @@ def _shard_loaders(args, rt, tr, va, tr_s, va_s, mean, std, cpad, s2d, drop_last
     kw = dict(device=rt.device, threads=args.loader_threads, seed=args.seed, mean=mean, std=std, cpad=cpad,
               return_index=idx, resample=resample)
     tr_l = ShardLoader(tr.path, args.batchsize, tr_s, tr_aug, tr_size, drop_last=drop_last_train,
-                       s2d=s2d, **kw)
+                       s2d=s2d, mix=_mix_sampler(args, rt), **kw)
     va_l = ShardLoader(va.path, args.batchsize, va_s, va_aug, va_size, s2d=s2d, **kw)
     return tr_l, va_l
 
@@ -145,7 +158,8 @@ def _device_synthetic(args, rt: Runtime):
     kw = dict(size=args.image_size, num_classes=args.num_classes, device=rt.device, mean=mean, std=std, cpad=cpad,
               s2d=s2d)
     B = args.batchsize
-    tr = SyntheticLoader(B, max(1, args.synthetic_train_size // B), seed=args.seed + 17 * rt.rank, **kw)
+    tr = SyntheticLoader(B, max(1, args.synthetic_train_size // B), seed=args.seed + 17 * rt.rank,
+                         mix=_mix_sampler(args, rt), **kw)
     va = SyntheticLoader(B, max(1, args.synthetic_val_size // B), seed=args.seed + 17 * rt.rank + 7, **kw)
     return tr, va, None, None
 
@@ -170,5 +184,5 @@ def build_data(args, rt: Runtime, drop_last_train=False):
     tr_l = build_loader(tr, args.batchsize, tr_s, workers=workers, drop_last=drop_last_train,
                         worker_init_fn=worker_init_fn)
     va_l = build_loader(va, args.batchsize, va_s, workers=workers, drop_last=False, worker_init_fn=worker_init_fn)
-    return (DevicePrefetcher(tr_l, rt.device, mean, std, cpad, s2d), DevicePrefetcher(va_l, rt.device, mean, std, cpad, s2d),
-            tr, va)
+    return (DevicePrefetcher(tr_l, rt.device, mean, std, cpad, s2d, mix=_mix_sampler(args, rt)),
+            DevicePrefetcher(va_l, rt.device, mean, std, cpad, s2d), tr, va)

@@ -681,6 +681,37 @@ def to_nhwc_s2d(src, nchw, in_scale, mean, std, block=2):
     return space_to_depth(x, block, False).contiguous()
 
 
+def _mix_rows(x, partner, blend, box):
+    """Mixup / CutMix of normalised NHWC rows (csrc/misc.hip, to_nhwc_pix_mix_kernel): inside
+    ``box[n]`` the partner's pixel, elsewhere ``blend * own + (1 - blend) * partner``; a row with
+    ``blend == 1`` keeps its own pixels outside the box as they are.  The CPU path's activations are
+    fp32, so the operands are not rounded to bf16 before the blend as the kernel's are."""
+    N, H, W, _ = x.shape
+    p = partner.long().clamp(0, N - 1)
+    xb = x[p]
+    bl = blend.float().view(N, 1, 1, 1)
+    out = torch.where(bl == 1, x, bl * x + (1 - bl) * xb)
+    ys = torch.arange(H, device=x.device).view(1, H, 1)
+    xs = torch.arange(W, device=x.device).view(1, 1, W)
+    b = box.long().view(N, 4)
+    y0, x0 = b[:, 0].clamp(0, H).view(N, 1, 1), b[:, 1].clamp(0, W).view(N, 1, 1)
+    y1, x1 = b[:, 2].clamp(0, H).view(N, 1, 1), b[:, 3].clamp(0, W).view(N, 1, 1)
+    inside = (ys >= y0) & (ys < y1) & (xs >= x0) & (xs < x1)
+    return torch.where(inside.unsqueeze(-1), xb, out)
+
+
+def to_nhwc_mix(src, nchw, cpad, in_scale, mean, std, partner, blend, box):
+    if cpad != 8 or (src.shape[1] if nchw else src.shape[3]) > 8:
+        raise RuntimeError("to_nhwc_mix: only the 8-slot layout (cpad 8, <= 8 channels) has a mixed kernel")
+    return _mix_rows(to_nhwc(src, nchw, cpad, in_scale, mean, std), partner, blend, box).contiguous()
+
+
+def to_nhwc_s2d_mix(src, nchw, in_scale, mean, std, partner, blend, box, block=2):
+    cq = 4 if block == 2 else 3
+    x = _mix_rows(to_nhwc(src, nchw, cq, in_scale, mean, std), partner, blend, box)
+    return space_to_depth(x, block, False).contiguous()
+
+
 def act_bwd(dy, y, act):
     if int(act) == 2:
         return (_f(dy) * _f(y) * (1 - _f(y))).to(dy.dtype)
@@ -774,6 +805,47 @@ def xent_bwd(logits, labels, C, grad_out, scale, smoothing, out_bf16):
     tgt.scatter_add_(1, labels.view(-1, 1), torch.full((B, 1), 1 - smoothing))
     d = torch.zeros(B, ld)
     d[:, :C] = (p - tgt) * (float(grad_out.float().reshape(-1)[0]) * scale)
+    return d.to(torch.bfloat16 if out_bf16 else torch.float32)
+
+
+def _label_pair(labels, partner, C):
+    B = labels.numel()
+    a = labels.view(-1).long()
+    b2 = a[partner.long().clamp(0, B - 1)]
+    valid = (a >= 0) & (a < C) & (b2 >= 0) & (b2 < C)
+    return a, b2, valid
+
+
+def xent_mix_fwd(logits, labels, partner, wlab, C, smoothing):
+    """Two-label cross-entropy (csrc/loss.hip, xent_mix_fwd_kernel): labels[b] with weight wlab[b],
+    labels[partner[b]] with 1 - wlab[b]; rank against labels[b]; a row with a label outside [0, C)
+    has loss 0."""
+    x = _f(logits)[:, :C]
+    a, b2, valid = _label_pair(labels, partner, C)
+    own = (a >= 0) & (a < C)
+    lse = torch.logsumexp(x, 1)
+    xa = torch.where(own, x.gather(1, a.clamp(0, C - 1).view(-1, 1)).squeeze(1), torch.zeros_like(lse))
+    xb = x.gather(1, b2.clamp(0, C - 1).view(-1, 1)).squeeze(1)
+    w = wlab.float()
+    loss = w * (lse - xa) + (1 - w) * (lse - xb)
+    if smoothing > 0:
+        loss = (1 - smoothing) * loss + smoothing * (lse - x.mean(1))
+    rank = (x > xa.unsqueeze(1)).sum(1).int()
+    return torch.where(valid, loss, torch.zeros_like(loss)), rank
+
+
+def xent_mix_bwd(logits, labels, partner, wlab, C, grad_out, scale, smoothing, out_bf16):
+    B, ld = logits.shape
+    x = _f(logits)[:, :C]
+    a, b2, valid = _label_pair(labels, partner, C)
+    p = torch.softmax(x, 1)
+    w = wlab.float().view(-1, 1)
+    tgt = torch.full_like(p, smoothing / C)
+    tgt.scatter_add_(1, a.clamp(0, C - 1).view(-1, 1), (1 - smoothing) * w)
+    tgt.scatter_add_(1, b2.clamp(0, C - 1).view(-1, 1), (1 - smoothing) * (1 - w))
+    g = float(grad_out.float().reshape(-1)[0]) * scale
+    d = torch.zeros(B, ld)
+    d[:, :C] = torch.where(valid.view(-1, 1), (p - tgt) * g, torch.zeros_like(p))
     return d.to(torch.bfloat16 if out_bf16 else torch.float32)
 
 

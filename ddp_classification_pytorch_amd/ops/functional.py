@@ -1610,10 +1610,45 @@ class _XEnt(Function):
         return d, None, None, None, None
 
 
-def cross_entropy(logits, labels, num_classes=None, smoothing=0.0, reduction="mean", return_rank=False):
-    """Softmax cross-entropy (one fused pass) -> loss [, rank of the true label]."""
+class _XEntMix(Function):
+    """The two-label form (Mixup / CutMix): ``xent_mix_fwd`` / ``xent_mix_bwd`` read the partner's
+    label in the kernel, so the mixed batch needs neither a gather nor a [B, C] target matrix."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, partner, wlab, C, smoothing, reduction):
+        loss_rows, rank = K(logits).xent_mix_fwd(logits, labels, partner, wlab, C, smoothing)
+        ctx.save_for_backward(logits, labels, partner, wlab)
+        ctx.C, ctx.smoothing, ctx.reduction = C, smoothing, reduction
+        ctx.mark_non_differentiable(rank)
+        ctx.set_materialize_grads(False)
+        loss = loss_rows.mean() if reduction == "mean" else loss_rows.sum()
+        return loss, rank
+
+    @staticmethod
+    def backward(ctx, g, _grank):
+        if g is None:
+            return None, None, None, None, None, None, None
+        logits, labels, partner, wlab = ctx.saved_tensors
+        B = logits.shape[0]
+        scale = 1.0 / B if ctx.reduction == "mean" else 1.0
+        d = K(logits).xent_mix_bwd(logits, labels, partner, wlab, ctx.C, g.reshape(1), scale, ctx.smoothing,
+                                   logits.dtype == torch.bfloat16)
+        return d, None, None, None, None, None, None
+
+
+def cross_entropy(logits, labels, num_classes=None, smoothing=0.0, reduction="mean", return_rank=False, mix=None):
+    """Softmax cross-entropy (one fused pass) -> loss [, rank of the true label].
+
+    ``mix=(partner, wlab)`` (int32 [B], fp32 [B]; data/mix.py) is the loss of a Mixup / CutMix batch:
+    row b carries ``labels[b]`` with weight ``wlab[b]`` and ``labels[partner[b]]`` with
+    ``1 - wlab[b]``.  The rank it returns is that of the row's OWN label, so training top-1 / top-3
+    under mixing are measured against the own label.  Without ``mix`` the one-label kernels run."""
     C = num_classes or logits.shape[1]
-    loss, rank = _XEnt.apply(logits, labels, C, float(smoothing), reduction)
+    if mix is not None:
+        partner, wlab = mix
+        loss, rank = _XEntMix.apply(logits, labels, partner, wlab, C, float(smoothing), reduction)
+    else:
+        loss, rank = _XEnt.apply(logits, labels, C, float(smoothing), reduction)
     return (loss, rank) if return_rank else loss
 
 
@@ -1817,17 +1852,32 @@ def s2d_for(s2d, h: int, w: int) -> int:
 
 
 def to_device_nhwc(images: torch.Tensor, mean=None, std=None, cpad: int = 8, nchw: bool = True, in_scale: float = 1.0,
-                   s2d=False):
+                   s2d=False, mix=None):
     """Image batch (uint8 or fp32, NCHW/NHWC, already on the target device) -> normalised
     NHWC activations with channels zero-padded to ``cpad``; ``s2d=True`` (or 2) emits the 2x2
     space-to-depth layout [N, H/2, W/2, 16] of the s2d stem (:func:`stem_conv_s2d`), ``s2d=4``
-    TResNet's 4x4 space-to-depth input [N, H/4, W/4, 48] (one pass from the images)."""
+    TResNet's 4x4 space-to-depth input [N, H/4, W/4, 48] (one pass from the images).
+
+    ``mix``: a Mixup / CutMix plan (data/mix.py: ``partner`` int32 [N], ``blend`` fp32 [N], ``box``
+    int32 [N, 4], on the images' device; a :class:`MixPlan` or such a tuple) mixes image n with image
+    ``partner[n]`` in the same pass.  Only the 8-slot and the space-to-depth layouts have a mixed
+    kernel: any other ``cpad`` refuses a plan."""
     if mean is not None and not torch.is_tensor(mean):
         mean = torch.tensor(mean, dtype=torch.float32, device=images.device)
     if std is not None and not torch.is_tensor(std):
         std = torch.tensor(std, dtype=torch.float32, device=images.device)
     blk = s2d_block(s2d)
-    if blk:
+    if mix is not None:
+        partner, blend, box = mix[0], mix[1], mix[2]
+        if blk:
+            out = K(images).to_nhwc_s2d_mix(images.contiguous(), nchw, in_scale, mean, std, partner, blend, box, blk)
+        else:
+            channels = images.shape[1] if nchw else images.shape[3]
+            if cpad != 8 or channels > 8:
+                raise ValueError(f"to_device_nhwc: a mix plan needs the 8-slot or a space-to-depth input layout "
+                                 f"(cpad 8, at most 8 channels), not cpad {cpad} with {channels} channels")
+            out = K(images).to_nhwc_mix(images.contiguous(), nchw, cpad, in_scale, mean, std, partner, blend, box)
+    elif blk:
         out = K(images).to_nhwc_s2d(images.contiguous(), nchw, in_scale, mean, std, blk)
     else:
         out = K(images).to_nhwc(images.contiguous(), nchw, cpad, in_scale, mean, std)
