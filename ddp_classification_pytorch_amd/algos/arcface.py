@@ -22,7 +22,7 @@ from ..engine.runtime import build_data, setup
 from ..models import build_model
 from ..models.heads import ArcMarginProduct, MLPHead
 from ..ops import functional as Fn
-from ..optim import StepLR, build_optimizer, optimizer_flags
+from ..optim import StepLR, build_ema, build_optimizer, optimizer_flags
 from ..parallel.ddp import attach_optimizer, wrap_ddp
 
 
@@ -72,6 +72,8 @@ def run(args):
         return Fn.arcface_rows(f, model.arc.weight, y, model.arc.s, model.arc.m, model.arc.easy_margin,
                                with_margin=args.arc_eval_with_labels)
 
-    loop = ClassificationLoop(args, rt, {"model": model}, opt, sched, train_data, val_data, fwd_train, fwd_eval,
-                              train_modules=[net])
+    models = {"model": model}
+    # --model-ema: over every model of the dict (backbone, embedding head and the ArcFace class centres)
+    loop = ClassificationLoop(args, rt, models, opt, sched, train_data, val_data, fwd_train, fwd_eval,
+                              train_modules=[net], ema=build_ema(args, models, opt))
     return loop.run()

@@ -13,7 +13,7 @@ from ..engine.runtime import build_data, setup
 from ..models import build_model
 from ..models.heads import ClassifierModel, MLPHead
 from ..ops import functional as Fn
-from ..optim import StepLR, build_optimizer, optimizer_flags
+from ..optim import StepLR, build_ema, build_optimizer, optimizer_flags
 from ..parallel.ddp import attach_optimizer, wrap_ddp
 
 
@@ -59,6 +59,7 @@ def run(args):
         x, y = batch[0], batch[1]
         return Fn.cross_entropy_rows(net(x), y, C)
 
-    loop = ClassificationLoop(args, rt, {"model": model}, opt, sched, train_data, val_data, fwd_train, fwd_eval,
-                              train_modules=[net])
+    models = {"model": model}
+    loop = ClassificationLoop(args, rt, models, opt, sched, train_data, val_data, fwd_train, fwd_eval,
+                              train_modules=[net], ema=build_ema(args, models, opt))
     return loop.run()

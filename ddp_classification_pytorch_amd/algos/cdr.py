@@ -105,7 +105,7 @@ def run(args):
     from ..engine.logger import rotate_results_file
     from ..engine.runtime import build_data, setup
     from ..ops import functional as Fn
-    from ..optim import MultiStepLR, build_optimizer
+    from ..optim import MultiStepLR, build_ema, build_optimizer
     from ..parallel.ddp import wrap_ddp
     import os
 
@@ -137,8 +137,10 @@ def run(args):
             state["epoch"] = epoch
             return super().train_epoch(epoch)
 
-    loop = _Loop(args, rt, {"model": model}, opt, sched, train_data, val_data, fwd_train, fwd_eval,
-                 post_backward=post_backward, scheduler_before_epoch=True, train_modules=[net])
+    models = {"model": model}
+    loop = _Loop(args, rt, models, opt, sched, train_data, val_data, fwd_train, fwd_eval,
+                 post_backward=post_backward, scheduler_before_epoch=True, train_modules=[net],
+                 ema=build_ema(args, models, opt))
     best = loop.run()
     hist = loop.logger.history.get("val/top1", [])
     if rt.is_main and hist:  # the reference crashes on an empty list here (CDR/main.py:381)

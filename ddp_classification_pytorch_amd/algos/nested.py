@@ -29,7 +29,7 @@ import torch.distributed as dist
 from ..engine.checkpoint import is_rank0, load_checkpoint
 from ..engine.logger import MetricsLogger
 from ..engine.loop import _check_transports, valid_count
-from ..config import refuse_mix
+from ..config import refuse_ema, refuse_mix
 from ..engine.runtime import build_data, setup
 from ..models.heads import NetClassifier
 from ..models.nested import NetFeat
@@ -111,6 +111,7 @@ def test_standard(net_feat, net_cls, val_data, nb_cls):
 
 def run(args):
     refuse_mix(args, "nested")
+    refuse_ema(args, "nested")
     rt = setup(args)
     logger = MetricsLogger(args.out_dir if rt.is_main else None)
     train_data, val_data, _, _ = build_data(args, rt, drop_last_train=True)

@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from ..engine.logger import MetricsLogger
 from ..engine.loop import ClassificationLoop
-from ..config import refuse_mix
+from ..config import refuse_ema, refuse_mix
 from ..engine.runtime import build_data, setup
 from ..ops import functional as Fn
 from ..optim import FusedSGD
@@ -154,6 +154,7 @@ def run(args):
     """Labels live in a device table indexed by dataset index, so corrections are
     visible immediately (persistent loader workers hold stale dataset copies)."""
     refuse_mix(args, "plc")
+    refuse_ema(args, "plc")
     from .baseline import build_classifier
 
     rt = setup(args)

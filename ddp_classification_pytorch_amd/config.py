@@ -142,6 +142,16 @@ def build_parser() -> argparse.ArgumentParser:
       help="with both alphas positive: probability of CutMix, else Mixup")
     a("--mix-mode", dest="mix_mode", default="batch", choices=["batch", "elem"],
       help="one draw per batch, or one per image")
+    # exponential moving average of the weights (optim/ema.py; baseline, arcface, cdr)
+    a("--model-ema", dest="model_ema", action="store_true",
+      help="keep an exponential moving average of every fp32 weight and BN statistic on the device, evaluate it "
+           "after the live model each epoch (val_ema) and checkpoint it; --resume needs a checkpoint written "
+           "with the flag")
+    a("--model-ema-decay", dest="model_ema_decay", type=float, default=0.9998,
+      help="EMA decay d: average += (1 - d) * (weight - average) after every optimizer step (a resumed run "
+           "keeps the checkpoint's decay and warm-up switch)")
+    a("--model-ema-warmup", dest="model_ema_warmup", action="store_true",
+      help="EMA decay warm-up: d_n = min(decay, (1 + n) / (10 + n)) at update n")
     # run control / persistence
     a("--seed", type=int, default=999)
     a("--out-dir", "--out_dir", "--result_dir", dest="out_dir", default="output")
@@ -250,6 +260,16 @@ def refuse_mix(args, workload: str):
     if given:
         raise ValueError(f"{', '.join(given)}: Mixup / CutMix is wired for --workload baseline only; the {workload} "
                          f"workload's head and loss take one label per image")
+
+
+def refuse_ema(args, workload: str):
+    """The workloads that run their own loops (nested, PLC) call this at start-up: a weight-EMA flag
+    there is an error, never silently ignored."""
+    defaults = dict(model_ema=False, model_ema_decay=0.9998, model_ema_warmup=False)
+    given = [f"--{k.replace('_', '-')}" for k, d in defaults.items() if getattr(args, k, d) != d]
+    if given:
+        raise ValueError(f"{', '.join(given)}: the weight EMA is wired for the baseline, arcface and cdr workloads; "
+                         f"the {workload} workload runs its own loop")
 
 
 def _cuda_available() -> bool:

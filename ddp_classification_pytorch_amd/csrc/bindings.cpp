@@ -2157,6 +2157,33 @@ void gnorm_finish(const Tensor& partials, const Tensor& slot_gs, double max_norm
                            clip_ctl_ptr(clip, "gnorm_finish"), cur_stream());
 }
 
+// Weight EMA over table rows (live, -, average, -, -, n): average = fma(omd, live - average, average) with
+// omd read from the device scalar; clip (optional): a set skip flag leaves every average untouched.
+static void check_mt_tables(const Tensor& table, const Tensor& chunks, const char* op) {
+  CHECK_DEV(table);
+  CHECK_DEV(chunks);
+  TORCH_CHECK(table.scalar_type() == at::kLong && table.is_contiguous() && table.dim() == 2 && table.size(1) == 6, op,
+              ": table int64 [n, 6]");
+  TORCH_CHECK(chunks.scalar_type() == at::kInt && chunks.is_contiguous() && chunks.dim() == 2 && chunks.size(1) == 2,
+              op, ": chunks int32 [k, 2]");
+}
+
+void mt_ema(const Tensor& table, const Tensor& chunks, const Tensor& omd, const c10::optional<Tensor>& clip) {
+  check_mt_tables(table, chunks, "mt_ema");
+  CHECK_DEV(omd);
+  TORCH_CHECK(omd.scalar_type() == at::kFloat && omd.numel() == 1, "mt_ema: omd float32[1]");
+  dcp::launch_mt_ema(reinterpret_cast<const dcp::MTEntry*>(table.data_ptr()),
+                     reinterpret_cast<const int2*>(chunks.data_ptr()), (int)chunks.size(0), omd.data_ptr<float>(),
+                     clip_ctl_ptr(clip, "mt_ema"), cur_stream());
+}
+
+// In-place exchange of each row's live tensor and average (pure copies of the bit patterns).
+void mt_swap(const Tensor& table, const Tensor& chunks) {
+  check_mt_tables(table, chunks, "mt_swap");
+  dcp::launch_mt_swap(reinterpret_cast<const dcp::MTEntry*>(table.data_ptr()),
+                      reinterpret_cast<const int2*>(chunks.data_ptr()), (int)chunks.size(0), cur_stream());
+}
+
 void mt_sgd(const Tensor& table, const Tensor& chunks, double lr, double momentum, double dampening, double wd,
             bool nesterov, bool first, double grad_scale) {
   CHECK_DEV(table);
@@ -2567,6 +2594,8 @@ TORCH_LIBRARY(dcp, m) {
         &gnorm_finish);
   m.def("cdr_threshold(Tensor table, Tensor chunks, Tensor state) -> Tensor", &cdr_threshold);
   m.def("mt_copy(Tensor table, Tensor chunks, float scale, int mode) -> ()", &mt_copy);
+  m.def("mt_ema(Tensor table, Tensor chunks, Tensor omd, Tensor? clip=None) -> ()", &mt_ema);
+  m.def("mt_swap(Tensor table, Tensor chunks) -> ()", &mt_swap);
   m.def(
       "conv_fwd_affine(Tensor x, Tensor w, int stride, int pad, Tensor scale, Tensor shift, int act, float slope, "
       "Tensor? res) -> Tensor",

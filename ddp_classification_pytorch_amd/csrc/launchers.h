@@ -356,6 +356,11 @@ void launch_gnorm_finish(const GnormPartial* partials, int nslots, const float* 
                          int skip_nonfinite, ClipCtl* ctl, hipStream_t s);
 // mode: bit 0 = source bf16, bit 1 = destination bf16 (MTEntry.p = destination, .g = source)
 void launch_mt_copy(const MTEntry* tab, const int2* chunks, int nchunks, float scale, int mode, hipStream_t s);
+// Weight EMA (MTEntry.p = live tensor, .s1 = its average): e = fma(*omd_dev, p - e, e) per element,
+// nothing written when ctl (optional) has its skip flag set; and the in-place exchange of p and s1.
+void launch_mt_ema(const MTEntry* tab, const int2* chunks, int nchunks, const float* omd_dev, const ClipCtl* ctl,
+                   hipStream_t s);
+void launch_mt_swap(const MTEntry* tab, const int2* chunks, int nchunks, hipStream_t s);
 void launch_mt_sgd(const MTEntry* tab, const int2* chunks, int nchunks, SgdHyper h, hipStream_t s);
 void launch_mt_adam(const MTEntry* tab, const int2* chunks, int nchunks, AdamHyper h, hipStream_t s);
 // LARS step: per-chunk sums of squares into partials [nchunks], per-tensor trust ratios (spans

@@ -18,6 +18,9 @@
 // * Global gradient-norm clipping and the non-finite skip in front of Adam, LARS (FusedSGD through it)
 //   and LAMB: per-chunk sums of g^2, one workgroup that merges them into a device control block
 //   (coefficient, skip flag, norm), which every update kernel reads.
+// * The exponential moving average of the weights over the same tables (mt_ema: e += omd (w - e), omd
+//   from a device scalar, honouring the skip flag) and the in-place exchange of weights and averages
+//   that evaluation on the average uses (mt_swap).
 // * CDR (CDR/main.py:186-204): threshold = k-th largest |g*w| over all 2-D/4-D
 //   parameters, found by a 4-pass 8-bit radix select over the float bit
 //   patterns (non-negative floats order like their uint32 bits) without
@@ -672,6 +675,115 @@ __global__ void __launch_bounds__(256) mt_copy_kernel(const MTEntry* __restrict_
     else
       ((float*)dst)[i] = v;
   }
+}
+
+// ---------------------------------------------------------------------------
+// Exponential moving average of the weights (optim/ema.py), over the same tables: MTEntry.p = the
+// live tensor w (read only), MTEntry.s1 = its average e.  Per element, in fp32,
+//   t  = w - e               (one rounding)
+//   e' = fma(omd, t, e)      (one rounding)
+// with omd ("one minus decay") read from a device scalar, so a replayed HIP graph follows a decay
+// warm-up.  e == w is a fixed point bit for bit.  The 16-byte and the 4-byte loop call the same
+// element function (the rule of sgd_elem): alignment never changes a bit.  With a clipping control
+// block whose skip flag is set the kernel writes nothing: a step the optimizer skipped leaves the
+// average (and the BN statistics a non-finite forward pass poisoned in the live model) alone.
+// 12 B / element; the loads of a chunk's (up to) four 16-byte rounds are issued before its stores.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ float ema_elem(float w, float e, float omd) { return fmaf(omd, __fsub_rn(w, e), e); }
+
+__global__ void __launch_bounds__(256) mt_ema_kernel(const MTEntry* __restrict__ tab, const int2* __restrict__ chunks,
+                                                     const float* __restrict__ omd_dev,
+                                                     const ClipCtl* __restrict__ ctl) {
+  if (clip_skip(ctl)) return;
+  const int2 ck = chunks[blockIdx.x];
+  const MTEntry e = tab[ck.x];
+  const int64_t base = (int64_t)ck.y * kChunk;
+  const int64_t end = min(e.n, base + kChunk);
+  const float omd = *omd_dev;
+  const uintptr_t mis = ((uintptr_t)(e.p + base) | (uintptr_t)(e.s1 + base)) & 15u;
+  if (mis == 0 && ((end - base) & 3) == 0) {  // uniform per chunk
+    const int n4 = (int)((end - base) >> 2);  // <= kChunk / 4 = 4 rounds of 256 lanes
+    const float4* __restrict__ w4 = (const float4*)(e.p + base);
+    float4* __restrict__ a4 = (float4*)(e.s1 + base);
+    float wv[4][4], av[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = threadIdx.x + r * 256;
+      if (j < n4) {
+        *(float4*)wv[r] = w4[j];
+        *(float4*)av[r] = a4[j];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = threadIdx.x + r * 256;
+      if (j < n4) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u) av[r][u] = ema_elem(wv[r][u], av[r][u], omd);
+        a4[j] = *(float4*)av[r];
+      }
+    }
+    return;
+  }
+  for (int64_t i = base + threadIdx.x; i < end; i += blockDim.x) e.s1[i] = ema_elem(e.p[i], e.s1[i], omd);
+}
+
+// In-place exchange of w (MTEntry.p) and e (MTEntry.s1): two loads and two stores per element, pure
+// copies of the bit patterns (integer lanes: no NaN payload, signed zero or denormal is touched).
+// Evaluation on the averaged weights swaps, evaluates, swaps back: no address changes, so a captured
+// graph, the optimizer's tables and the bucket views stay valid.  16 B / element.
+__global__ void __launch_bounds__(256) mt_swap_kernel(const MTEntry* __restrict__ tab,
+                                                      const int2* __restrict__ chunks) {
+  const int2 ck = chunks[blockIdx.x];
+  const MTEntry e = tab[ck.x];
+  const int64_t base = (int64_t)ck.y * kChunk;
+  const int64_t end = min(e.n, base + kChunk);
+  const uintptr_t mis = ((uintptr_t)(e.p + base) | (uintptr_t)(e.s1 + base)) & 15u;
+  if (mis == 0 && ((end - base) & 3) == 0) {  // uniform per chunk
+    const int n4 = (int)((end - base) >> 2);
+    uint4* __restrict__ w4 = (uint4*)(e.p + base);
+    uint4* __restrict__ a4 = (uint4*)(e.s1 + base);
+    // Values are named and unconditionally written, never conditionally filled arrays (those left
+    // the registers for LDS and scratch).  A whole chunk, the common case, is straight-line code: its
+    // eight 16-byte loads are issued before the first store.  A tensor's last chunk takes the loop.
+    if (n4 == kChunk / 4) {
+      const int j = threadIdx.x;
+      const uint4 x0 = w4[j], x1 = w4[j + 256], x2 = w4[j + 512], x3 = w4[j + 768];
+      const uint4 y0 = a4[j], y1 = a4[j + 256], y2 = a4[j + 512], y3 = a4[j + 768];
+      w4[j] = y0;
+      w4[j + 256] = y1;
+      w4[j + 512] = y2;
+      w4[j + 768] = y3;
+      a4[j] = x0;
+      a4[j + 256] = x1;
+      a4[j + 512] = x2;
+      a4[j + 768] = x3;
+      return;
+    }
+#pragma unroll 4
+    for (int j = threadIdx.x; j < n4; j += 256) {
+      const uint4 x = w4[j];
+      const uint4 y = a4[j];
+      w4[j] = y;
+      a4[j] = x;
+    }
+    return;
+  }
+  uint32_t* w = (uint32_t*)e.p;
+  uint32_t* a = (uint32_t*)e.s1;
+  for (int64_t i = base + threadIdx.x; i < end; i += blockDim.x) {
+    const uint32_t x = w[i], y = a[i];
+    w[i] = y;
+    a[i] = x;
+  }
+}
+
+void launch_mt_ema(const MTEntry* tab, const int2* chunks, int nchunks, const float* omd_dev, const ClipCtl* ctl,
+                   hipStream_t s) {
+  if (nchunks) hipLaunchKernelGGL(mt_ema_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks, omd_dev, ctl);
+}
+void launch_mt_swap(const MTEntry* tab, const int2* chunks, int nchunks, hipStream_t s) {
+  if (nchunks) hipLaunchKernelGGL(mt_swap_kernel, dim3(nchunks), dim3(256), 0, s, tab, chunks);
 }
 
 void launch_mt_copy(const MTEntry* tab, const int2* chunks, int nchunks, float scale, int mode, hipStream_t s) {

@@ -24,6 +24,8 @@ counter the captured step increments, optim/fused.py).
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 import os
 
 import torch
@@ -37,6 +39,23 @@ def _stale_weights():
     from ..ops import functional as Fn
 
     Fn.bump_weight_generation()
+
+
+@contextlib.contextmanager
+def _no_gc_during_capture():
+    """Collect garbage now and keep the cyclic collector off while a step is captured.  A collector pass
+    inside the capture would finalize whatever dead cycles the process carries -- an earlier run's loop
+    with its ``CUDAGraph``, whose destructor synchronizes the device, or tensors whose release records
+    events -- and HIP refuses such calls on a capturing stream: the process aborts.  torch's own
+    ``torch.cuda.graph`` no longer collects on entry."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 class HostCounters:
@@ -143,7 +162,7 @@ class GraphedStep:
         if counters is not None:
             counters.begin_capture()
         self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode=_capture_mode()):
+        with _no_gc_during_capture(), torch.cuda.graph(self.graph, capture_error_mode=_capture_mode()):
             self.out = step_fn()
         if counters is not None:
             counters.end_capture()
@@ -205,7 +224,7 @@ class StepGrapher:
             if self.counters is not None:
                 self.counters.begin_capture()
             self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, capture_error_mode=_capture_mode()):
+            with _no_gc_during_capture(), torch.cuda.graph(self.graph, capture_error_mode=_capture_mode()):
                 self.out = self.fn(*self.static)
             if self.counters is not None:
                 self.counters.end_capture()

@@ -25,7 +25,11 @@ Differences from the reference, all deliberate:
   sync beyond the log interval's), a per-rank heartbeat file
   (``heartbeat_rank<r>.txt``: wall time, step, loss every ``--heartbeat-every``
   steps, so a hung or dead rank is visible), and ``--profile``: a torch.profiler
-  (roctracer) trace of a few steps of the first epoch into ``<out-dir>/profile``.
+  (roctracer) trace of a few steps of the first epoch into ``<out-dir>/profile``;
+* ``--model-ema``: an exponential moving average of the weights (optim/ema.py) updated inside the
+  step -- and so inside the captured HIP graph --, evaluated after the live model under
+  ``ema.applied()`` (``val_ema`` records, ``VAL-EMA`` lines) and carried by the checkpoints;
+  ``best.pth`` is still chosen by the live model's top-1.
 """
 from __future__ import annotations
 
@@ -74,12 +78,13 @@ class ClassificationLoop:
 
     def __init__(self, args, rt, models: dict, optimizer, scheduler, train_data, val_data, forward_train,
                  forward_eval, post_backward=None, logger: MetricsLogger = None, scheduler_before_epoch=False,
-                 train_modules=None):
+                 train_modules=None, ema=None):
         self.args, self.rt = args, rt
         self.models, self.optimizer, self.scheduler = models, optimizer, scheduler
         self.train_data, self.val_data = train_data, val_data
         self.forward_train, self.forward_eval = forward_train, forward_eval
         self.post_backward = post_backward
+        self.ema = ema  # optim.WeightEMA or None (--model-ema)
         self.logger = logger or MetricsLogger(args.out_dir if rt.is_main else None)
         self.scheduler_before_epoch = scheduler_before_epoch  # CDR steps its scheduler before training (:365-366)
         self.train_modules = train_modules or list(models.values())
@@ -113,12 +118,18 @@ class ClassificationLoop:
         self.global_step = int(extra.get("global_step", 0))
         self.best = float(extra.get("best", -1.0))
         self._warmup_state = extra.get("warmup")
+        if self.ema is not None:
+            if extra.get("ema") is None:
+                raise RuntimeError(f"--model-ema: {path} carries no weight EMA (it was written without the flag)")
+            self.ema.load_state_dict(extra["ema"])
         self.logger.line(f"resumed from {path}: epoch {self.start_epoch}, step {self.global_step}")
 
     def save(self, epoch, val_top1):
         kw = dict(epoch=epoch, global_step=self.global_step, best=max(self.best, val_top1),
                   warmup=self.warmup.state_dict() if self.warmup is not None else None,
                   config={k: v for k, v in vars(self.args).items() if isinstance(v, (int, float, str, bool, list))})
+        if self.ema is not None:
+            kw["ema"] = self.ema.state_dict()
         sched = {"sched": self.scheduler} if self.scheduler is not None else None
         save_checkpoint(self._ckpt("last.pth"), self.models, {"opt": self.optimizer}, sched, **kw)
         if val_top1 > self.best:
@@ -133,6 +144,10 @@ class ClassificationLoop:
         if self.post_backward is not None:
             self.post_backward()
         self.optimizer.step()
+        if self.ema is not None:
+            # behind the step on this stream (the bucket engine's per-bucket steps included: its
+            # finalize made this stream wait for the communication stream)
+            self.ema.update()
         # detached: a loss kept alive until the next step would keep this step's autograd graph --
         # and with it the parameters' AccumulateGrad nodes, bound to this step's stream -- alive
         # into a HIP-graph capture, whose gradient accumulation would then sync with that stream
@@ -150,7 +165,8 @@ class ClassificationLoop:
             from .graph import HostCounters, StepGrapher
 
             mods = list(self.models.values()) + list(self.train_modules)
-            self._grapher = StepGrapher(self._train_step, warmup=2, counters=HostCounters(mods, [self.optimizer]))
+            counted = [self.optimizer] + ([self.ema] if self.ema is not None else [])  # on_graph_replay() hooks
+            self._grapher = StepGrapher(self._train_step, warmup=2, counters=HostCounters(mods, counted))
 
     def _setup_warmup(self):
         """The ramp's target is the configured ``--lr`` (or the scheduler's base LR), never the
@@ -229,6 +245,8 @@ class ClassificationLoop:
                 self.poly.set(self.global_step)
             if self._dev_lr:
                 self.optimizer.push_lr()
+            if self.ema is not None:
+                self.ema.push_decay()  # the decay of this update, read from the device by the (replayed) step
             if self._grapher is not None and (self._dev_lr or not (in_warmup or self.poly is not None)):
                 loss, rank = self._grapher(*batch)
             elif self._grapher is not None:
@@ -327,6 +345,13 @@ class ClassificationLoop:
                 self.logger.line(f"VAL Epoch {epoch + 1}: loss {va['loss']:.4f} top1 {100 * va['top1']:.3f} "
                                  f"top3 {100 * va['top3']:.3f} (n={int(va['count'])}) | train loss {tr['loss']:.4f} "
                                  f"top1 {100 * tr['top1']:.3f} ({tr['time']:.1f}s)")
+                if self.ema is not None:
+                    with self.ema.applied():  # the live model computes on the averages; every bit comes back
+                        ve = self.evaluate()
+                    self.logger.log("val_ema", epoch=epoch, updates=self.ema.num_updates, **ve)
+                    self.logger.line(f"VAL-EMA Epoch {epoch + 1}: loss {ve['loss']:.4f} top1 {100 * ve['top1']:.3f} "
+                                     f"top3 {100 * ve['top3']:.3f} (n={int(ve['count'])}, "
+                                     f"{self.ema.num_updates} updates)")
             if self.scheduler is not None and not self.scheduler_before_epoch:
                 self.scheduler.step()
             if (epoch + 1) % a.save_every == 0 or epoch + 1 == a.epochs:

@@ -1006,3 +1006,27 @@ def se_gate_bwd(dg, g, h, p, w1t, w2t):
     db1 = _f(d1).sum(0)
     dp = (_f(d1) @ _f(w1t[:, :R]).t()).to(p.dtype)
     return dp, dw1, db1, dw2, db2
+
+
+def mt_ema(pairs, omd, skip=False):
+    """Weight EMA, the CPU path of the ``mt_ema`` kernel.  Where the kernel takes a device table of
+    pointers, this takes the ``(live, average)`` fp32 tensor pairs themselves; ``omd`` is the
+    float32[1] "one minus decay" scalar and ``skip`` the clipping control block's skip flag.  Per
+    element ``t = w - e`` is formed in fp32 and ``e' = fma(omd, t, e)`` is emulated by ``e + omd t`` in
+    fp64 (the product of two fp32 numbers is exact there) rounded to fp32."""
+    if skip:
+        return
+    o = omd.detach().reshape(()).to(torch.float64)
+    for w, e in pairs:
+        t = w.detach().to(torch.float32) - e
+        e.copy_((e.to(torch.float64) + o * t.to(torch.float64)).to(torch.float32))
+
+
+def mt_swap(pairs):
+    """In-place exchange of every ``(live, average)`` pair, the CPU path of the ``mt_swap`` kernel:
+    copies of the bit patterns (through int32 views: a NaN payload survives)."""
+    for w, e in pairs:
+        wi, ei = w.detach().view(torch.int32), e.view(torch.int32)
+        tmp = wi.clone()
+        wi.copy_(ei)
+        ei.copy_(tmp)

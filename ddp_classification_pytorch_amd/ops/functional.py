@@ -118,6 +118,7 @@ class _MTWeightCache:
     def __init__(self):
         self.entries = {}   # (id(w), co_pad, transposed, ci) -> entry dict
         self.tables = {}    # tuple of entry ids -> (entries tensor, blocks tensor)
+        self.captured = set()  # keys of the tables a HIP-graph capture recorded a launch with
 
     @staticmethod
     def _stamp(w):
@@ -177,8 +178,13 @@ class _MTWeightCache:
             ent = table_to_device(rows, torch.int64, dev)
             blk = table_to_device(blocks, torch.int32, dev)
             if len(self.tables) > 16:
-                self.tables.clear()
+                # a captured HIP graph replays its mt_weight_prep launch with the addresses of the tables
+                # it was captured with: those are never dropped (a model built after the capture
+                # registers its weights one by one, one small table each, and would evict them)
+                self.tables = {k: v for k, v in self.tables.items() if k in self.captured}
             tab = self.tables[tkey] = (ent, blk)
+        if torch.cuda.is_current_stream_capturing():
+            self.captured.add(tkey)
         _ext.hip_ops().mt_weight_prep(*tab)
         for _, e, w in stale:
             e["stamp"] = self._stamp(w)

@@ -1,3 +1,4 @@
+from .ema import WeightEMA
 from .fused import FusedAdam, FusedLAMB, FusedLARS, FusedSGD
 from .schedulers import LinearWarmup, MultiStepLR, PolyDecay, StepLR
 
@@ -51,5 +52,14 @@ def optimizer_flags(args):
                 lamb_phi_min=getattr(args, "lamb_phi_min", 0.0), lamb_phi_max=getattr(args, "lamb_phi_max", float("inf")))
 
 
+def build_ema(args, models, optimizer=None):
+    """``--model-ema``: the :class:`WeightEMA` over every model of the loop's ``models`` dict (the optimizer's
+    non-finite skip is honoured); None without the flag."""
+    if not getattr(args, "model_ema", False):
+        return None
+    return WeightEMA(models, decay=getattr(args, "model_ema_decay", 0.9998),
+                     warmup=getattr(args, "model_ema_warmup", False), optimizer=optimizer)
+
+
 __all__ = ["FusedSGD", "FusedAdam", "FusedLARS", "FusedLAMB", "LinearWarmup", "MultiStepLR", "PolyDecay", "StepLR",
-           "build_optimizer", "optimizer_flags"]
+           "WeightEMA", "build_ema", "build_optimizer", "optimizer_flags"]

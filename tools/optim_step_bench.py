@@ -1,7 +1,7 @@
 """Step time of the fused optimizers over ResNet-50's parameter tensors (25.6M elements): FusedLARS
 against FusedSGD, FusedLAMB against FusedAdam.
 
-    python tools/optim_step_bench.py [--steps 200] [--rounds 5] [--arms sgd,lars,adam,lamb] [--clip] [--out FILE]
+    python tools/optim_step_bench.py [--steps 200] [--rounds 5] [--arms sgd,lars,adam,lamb] [--clip] [--ema] [--out FILE]
 
 Every optimizer steps its own copy of the same parameters and gradients (weight decay 1e-4; momentum
 0.9 for SGD / LARS), eagerly and as a replayed HIP graph of one step.  Timing: HIP events around
@@ -17,6 +17,10 @@ second read is served from.
 ``--clip`` adds a clipped arm per optimizer (``max_grad_norm=1``, ``skip_nonfinite``; the gradients'
 norm is 5, so every step clips): the norm pass reads g once more (+4 B per element) and one
 workgroup merges the 6,240 chunk sums.  It also times the norm pass and the finish kernel alone.
+
+``--ema`` adds two arms over the tensors a WeightEMA tracks in a ResNet-50 built here (parameters and BN
+running statistics): ``ema`` (mt_ema: reads w and e, writes e, 12 B per element) and ``swap`` (mt_swap:
+reads and writes both, 16 B), next to ``sgd`` in the same alternating blocks.
 """
 import argparse
 import os
@@ -29,7 +33,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from ddp_classification_pytorch_amd import _ext  # noqa: E402
 from ddp_classification_pytorch_amd.models import build_model  # noqa: E402
-from ddp_classification_pytorch_amd.optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD  # noqa: E402
+from ddp_classification_pytorch_amd.optim import FusedAdam, FusedLAMB, FusedLARS, FusedSGD, WeightEMA  # noqa: E402
 
 # one adaptive group over every tensor for LARS / LAMB: the full traffic (build_optimizer's default
 # split leaves the 1-D tensors, 0.2 % of the elements, non-adaptive)
@@ -44,6 +48,9 @@ CLIP = dict(max_grad_norm=1.0, skip_nonfinite=True)
 for _k in list(ARMS):
     ARMS[_k + "+clip"] = (ARMS[_k][0], dict(ARMS[_k][1], **CLIP), ARMS[_k][2] + 4)
 CLIP_RATIOS = tuple((k + "+clip", k) for k in ("sgd", "adam", "lars", "lamb"))
+ARMS["ema"] = (None, {}, 12)
+ARMS["swap"] = (None, {}, 16)
+EMA_RATIOS = (("ema", "sgd"), ("swap", "sgd"))
 
 
 def _arm(cls, shapes, dev, seed, **kw):
@@ -72,13 +79,17 @@ def main(argv=None):
     ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--clip", action="store_true", help="add a clipped arm per optimizer, the norm pass and the "
                                                         "finish kernel alone")
+    ap.add_argument("--ema", action="store_true", help="add the weight-EMA update and exchange kernels over "
+                                                       "ResNet-50's tracked tensors, next to sgd")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("optim_step_bench needs the GPU: a step time is not measured on the CPU")
     _ext.hip_ops()
     dev = torch.device("cuda", 0)
-    names = [k for k in a.arms.split(",") if k]
+    names = [k for k in a.arms.split(",") if k and k not in ("ema", "swap")]
+    if a.ema and "sgd" not in names:
+        names.insert(0, "sgd")
     if a.clip:
         names += [k + "+clip" for k in names if "+" not in k]
     shapes = [tuple(p.shape) for p in build_model("resnet50", num_classes=1000).parameters()]
@@ -88,6 +99,16 @@ def main(argv=None):
              f"# device: {torch.cuda.get_device_name(0)}"]
     opts = {k: _arm(ARMS[k][0], shapes, dev, 1, **ARMS[k][1])[1] for k in names}
     arms = {k: o.step for k, o in opts.items()}
+    counts = {k: n for k in names}
+    if a.ema:
+        ema = WeightEMA(build_model("resnet50", num_classes=1000).to(dev), decay=0.9998)
+        table, chunks = ema._tables()
+        arms["ema"] = ema.update
+        arms["swap"] = lambda: _ext.hip_ops().mt_swap(table, chunks)  # the kernel alone: no generation bump
+        counts["ema"] = counts["swap"] = sum(ema.average_of(k).numel() for k in ema.keys())
+        names += ["ema", "swap"]
+        lines.append(f"# ema / swap: {len(ema.keys())} tracked tensors, {counts['ema']} elements, {chunks.shape[0]} "
+                     "chunks (parameters and BN running statistics)")
     for f in arms.values():  # first launches, tables, the device learning rate and step counters
         for _ in range(3):
             f()
@@ -107,7 +128,7 @@ def main(argv=None):
                 f()
             graphs[name] = g.replay
         modes["graph"] = graphs
-    bytes_per = {k: ARMS[k][2] * n for k in names}
+    bytes_per = {k: ARMS[k][2] * counts[k] for k in names}
     res = {}
     for mode in [m for m in a.modes.split(",") if m in modes]:
         fns = modes[mode]
@@ -122,7 +143,7 @@ def main(argv=None):
             res[(mode, k)] = med
             lines.append(f"{mode:5s} {k:4s} {med:8.1f} us  [{min(t[k]):.1f} .. {max(t[k]):.1f}]   "
                          f"{bytes_per[k] / 1e6:.0f} MB accounted -> {bytes_per[k] / med / 1e6:.2f} TB/s")
-        for num, den in RATIOS + CLIP_RATIOS:
+        for num, den in RATIOS + CLIP_RATIOS + EMA_RATIOS:
             if num in fns and den in fns:
                 ratio = res[(mode, num)] / res[(mode, den)]
                 lines.append(f"{mode:5s} {num.upper()} / {den.upper()} step-time ratio {ratio:.3f}  (traffic model "
