@@ -46,7 +46,8 @@ def build_arcface(args):
 
         load_pretrained(backbone, args.pretrained)
     embed = MLPHead(backbone.feat_dim, args.hidden, args.embed_dim, log_softmax=True)
-    arc = ArcMarginProduct(args.embed_dim, args.num_classes, s=args.arc_s, m=args.arc_m, easy_margin=args.easy_margin)
+    arc = ArcMarginProduct(args.embed_dim, args.num_classes, s=args.arc_s, m=args.arc_m, easy_margin=args.easy_margin,
+                           sub_centers=args.arc_sub_centers)
     return ArcFaceModel(backbone, embed, arc)
 
 

@@ -48,7 +48,9 @@ def _torch_paths():
 COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1"]
 # per-file extras: the stem kernel's statistics run beside MFMAs, where packed fp32 (which the
 # SLP vectorizer forms from adjacent scalar adds / FMAs) issues slower than scalar fp32
-FILE_FLAGS = {"stem.hip": ["-fno-slp-vectorize"]}
+FILE_FLAGS = {"stem.hip": ["-fno-slp-vectorize"],
+              # the sub-centre head's softmax tail sits between two MFMA groups: scalar fp32 there too
+              "arcface_sub.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _headers():

@@ -180,6 +180,9 @@ def build_parser() -> argparse.ArgumentParser:
     a("--arc-eval-with-labels", action="store_true", default=True,
       help="reference behaviour: margin applied with true labels at eval (ARCFACE/arc_main.py:368)")
     a("--arc-eval-plain-cosine", dest="arc_eval_with_labels", action="store_false")
+    a("--arc-sub-centers", type=int, default=1,
+      help="Sub-center ArcFace: K centres per class, a sample scored against the nearest one (1: plain ArcFace; "
+           "the fused head covers 2..4 at an embedding width <= 256)")
     # CDR (unused reference flags accepted for CLI compatibility)
     a("--noise_rate", "--noise-rate", dest="noise_rate", type=float, default=0.2)
     a("--num_gradual", type=int, default=10)

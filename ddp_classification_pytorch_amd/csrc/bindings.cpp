@@ -2101,6 +2101,101 @@ Tensor arcface_fused_dw(const Tensor& xn, const Tensor& xnT, const Tensor& wn, c
   return dw;
 }
 
+// Fused Sub-center ArcFace head (arcface_sub.hip).  W [C][K][D] fp32 -> (wn [Wp][Dp], wnT [Dp][Wp],
+// inverse norms [Wp]) in the kernels' planar row order
+std::tuple<Tensor, Tensor, Tensor> arcface_sub_l2norm_t(const Tensor& w, int64_t Dp, double eps) {
+  CHECK_DEV(w);
+  CHECK_CONTIG(w);
+  CHECK_F32(w);
+  TORCH_CHECK(w.dim() == 3, "arcface_sub_l2norm_t: weight [C][K][D]");
+  const int C = w.size(0), K = w.size(1), D = w.size(2);
+  TORCH_CHECK(K >= 2 && K <= 4 && (Dp == 128 || Dp == 256) && D <= Dp && C >= 1,
+              "arcface_sub: K in {2, 3, 4}, D <= Dp in {128, 256}");
+  const int64_t Wp = dcp::arcface_sub_rows(C, K);
+  auto y = at::empty({Wp, Dp}, w.options().dtype(at::kBFloat16));
+  auto yT = at::empty({Dp, Wp}, w.options().dtype(at::kBFloat16));
+  auto inv = at::empty({Wp}, w.options());
+  TORCH_CHECK(dcp::launch_arcface_sub_l2norm_t(w.data_ptr<float>(), C, K, D, (int)Dp, bpm(y), bpm(yT),
+                                               inv.data_ptr<float>(), (float)eps, cur_stream()),
+              "arcface_sub_l2norm_t: unsupported shape");
+  return {y, yT, inv};
+}
+
+// -> loss [B], rank [B], lse [Bp], (target logit, d phi / d cos) [Bp][2], sub_idx [Bp] (int32)
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> arcface_sub_fwd(const Tensor& xn, const Tensor& wn,
+                                                                   const Tensor& labels, int64_t B, int64_t C,
+                                                                   int64_t K, double s, double m, bool easy) {
+  CHECK_ACT(xn);
+  CHECK_ACT(wn);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda() && labels.numel() == B, "arcface_sub labels");
+  TORCH_CHECK(K >= 2 && K <= 4 && C >= 1, "arcface_sub: K in {2, 3, 4}");
+  const int Bp = xn.size(0), Dp = xn.size(1), Wp = dcp::arcface_sub_rows(C, K);
+  TORCH_CHECK(wn.size(0) == Wp && wn.size(1) == Dp && Bp >= B && B >= 1, "arcface_sub_fwd shapes");
+  const int S = dcp::arcface_fused_fwd_splits(Bp, Wp);
+  auto loss = at::empty({B}, f32_like(xn));
+  auto rank = at::empty({B}, xn.options().dtype(at::kInt));
+  auto lse = at::empty({Bp}, f32_like(xn));
+  auto lab = at::empty({Bp, 2}, f32_like(xn));
+  auto sub = at::empty({Bp}, xn.options().dtype(at::kInt));
+  auto part = at::empty({(int64_t)S * Bp * 4}, f32_like(xn));
+  TORCH_CHECK(dcp::launch_arcface_sub_fwd(bp(xn), bp(wn), labels.data_ptr<int64_t>(), B, Bp, C, K, Dp, (float)s,
+                                          (float)m, easy, lab.data_ptr<float>(), sub.data_ptr<int>(),
+                                          part.data_ptr<float>(), loss.data_ptr<float>(), rank.data_ptr<int>(),
+                                          lse.data_ptr<float>(), cur_stream()),
+              "arcface_sub_fwd: unsupported shape (B padded to 64, D padded to 128 / 256)");
+  return {loss, rank, lse, lab, sub};
+}
+
+Tensor arcface_sub_dx(const Tensor& xn, const Tensor& wn, const Tensor& wnT, const Tensor& labels, const Tensor& lse,
+                      const Tensor& lab, const Tensor& sub, const Tensor& grad_out, double scale, const Tensor& inv_x,
+                      int64_t B, int64_t C, int64_t K, int64_t D, double s, bool out_bf16) {
+  CHECK_ACT(xn);
+  CHECK_ACT(wn);
+  CHECK_ACT(wnT);
+  TORCH_CHECK(K >= 2 && K <= 4 && C >= 1, "arcface_sub: K in {2, 3, 4}");
+  const int Bp = xn.size(0), Dp = xn.size(1), Wp = dcp::arcface_sub_rows(C, K);
+  TORCH_CHECK(wn.size(0) == Wp && wn.size(1) == Dp && wnT.size(0) == Dp && wnT.size(1) == Wp && Bp >= B &&
+                  labels.numel() == B && lse.numel() == Bp && lab.numel() == 2 * Bp && sub.numel() == Bp &&
+                  inv_x.numel() == Bp && sub.scalar_type() == at::kInt,
+              "arcface_sub_dx shapes");
+  auto g = grad_out.to(at::kFloat).contiguous();
+  const int S = dcp::arcface_fused_dx_splits(Bp, Wp);
+  auto part = at::empty({(int64_t)S * Bp * Dp}, f32_like(xn));
+  auto dx = at::empty({B, D}, xn.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+  TORCH_CHECK(dcp::launch_arcface_sub_dx(bp(xn), bp(wn), bp(wnT), labels.data_ptr<int64_t>(), B, Bp, C, K, Dp, D,
+                                         (float)s, lab.data_ptr<float>(), sub.data_ptr<int>(), lse.data_ptr<float>(),
+                                         g.data_ptr<float>(), (float)scale, inv_x.data_ptr<float>(),
+                                         part.data_ptr<float>(), dx.data_ptr(), out_bf16, cur_stream()),
+              "arcface_sub_dx: unsupported shape (B padded to 64, D <= Dp in {128, 256})");
+  return dx;
+}
+
+Tensor arcface_sub_dw(const Tensor& xn, const Tensor& xnT, const Tensor& wn, const Tensor& labels, const Tensor& lse,
+                      const Tensor& lab, const Tensor& sub, const Tensor& grad_out, double scale, const Tensor& inv_w,
+                      int64_t B, int64_t C, int64_t K, int64_t D, double s) {
+  CHECK_ACT(xn);
+  CHECK_ACT(xnT);
+  CHECK_ACT(wn);
+  TORCH_CHECK(K >= 2 && K <= 4 && C >= 1, "arcface_sub: K in {2, 3, 4}");
+  const int Bp = xn.size(0), Dp = xn.size(1), Wp = dcp::arcface_sub_rows(C, K);
+  TORCH_CHECK(wn.size(0) == Wp && wn.size(1) == Dp && xnT.size(0) == Dp && xnT.size(1) == Bp && Bp >= B &&
+                  labels.numel() == B && lse.numel() == Bp && lab.numel() == 2 * Bp && sub.numel() == Bp &&
+                  inv_w.numel() == Wp && sub.scalar_type() == at::kInt,
+              "arcface_sub_dw shapes");
+  auto g = grad_out.to(at::kFloat).contiguous();
+  auto dw = at::empty({C, K, D}, f32_like(xn));
+  const int S = dcp::arcface_fused_dw_splits(Bp, Wp);
+  auto part = at::empty({S > 1 ? (int64_t)S * Wp * Dp : 1}, f32_like(xn));
+  auto info = at::empty({(int64_t)Bp * 4}, f32_like(xn));  // per-row (label and sub_idx, t, dphi, lse)
+  TORCH_CHECK(dcp::launch_arcface_sub_dw(bp(xn), bp(xnT), bp(wn), labels.data_ptr<int64_t>(), B, Bp, C, K, Dp, D,
+                                         (float)s, lab.data_ptr<float>(), sub.data_ptr<int>(), lse.data_ptr<float>(),
+                                         g.data_ptr<float>(), (float)scale, inv_w.data_ptr<float>(),
+                                         part.data_ptr<float>(), info.data_ptr<float>(), dw.data_ptr<float>(),
+                                         cur_stream()),
+              "arcface_sub_dw: unsupported shape (B padded to 64, D <= Dp in {128, 256})");
+  return dw;
+}
+
 // ---------------------------------------------------------------------------
 // optimizers (multi-tensor). table: int64 [n,6] = (p, g, s1, s2, shadow, numel); chunks int32 [k,2]
 // ---------------------------------------------------------------------------
@@ -2563,6 +2658,14 @@ TORCH_LIBRARY(dcp, m) {
         "float scale, Tensor inv_x, int B, int C, int D, float s, bool out_bf16) -> Tensor", &arcface_fused_dx);
   m.def("arcface_fused_dw(Tensor xn, Tensor xnT, Tensor wn, Tensor labels, Tensor lse, Tensor lab, Tensor grad_out, "
         "float scale, Tensor inv_w, int B, int C, int D, float s) -> Tensor", &arcface_fused_dw);
+  m.def("arcface_sub_l2norm_t(Tensor w, int Dp, float eps) -> (Tensor, Tensor, Tensor)", &arcface_sub_l2norm_t);
+  m.def("arcface_sub_fwd(Tensor xn, Tensor wn, Tensor labels, int B, int C, int K, float s, float m, bool easy) -> "
+        "(Tensor, Tensor, Tensor, Tensor, Tensor)", &arcface_sub_fwd);
+  m.def("arcface_sub_dx(Tensor xn, Tensor wn, Tensor wnT, Tensor labels, Tensor lse, Tensor lab, Tensor sub, Tensor "
+        "grad_out, float scale, Tensor inv_x, int B, int C, int K, int D, float s, bool out_bf16) -> Tensor",
+        &arcface_sub_dx);
+  m.def("arcface_sub_dw(Tensor xn, Tensor xnT, Tensor wn, Tensor labels, Tensor lse, Tensor lab, Tensor sub, Tensor "
+        "grad_out, float scale, Tensor inv_w, int B, int C, int K, int D, float s) -> Tensor", &arcface_sub_dw);
   m.def(
       "arcface_fwd(Tensor cosv, Tensor labels, int C, float s, float m, bool easy, bool want_logits) -> (Tensor, "
       "Tensor, Tensor, Tensor)",

@@ -473,6 +473,24 @@ bool launch_arcface_fused_dw(const bf16* xn, const bf16* xnT, const bf16* wn, co
                              int C, int Cp, int Dp, int D, float s, const float* lab, const float* lse,
                              const float* gout, float scale, const float* inv_w, float* part, float* info,
                              float* dw, hipStream_t st);
+// Fused Sub-center ArcFace head (arcface_sub.hip): K in {2, 3, 4} centres per class, Dp in {128, 256}.
+// The centre operands wn [Wp][Dp], wnT [Dp][Wp], inv_w [Wp] use the planar row order of that file,
+// Wp = arcface_sub_rows(C, K); xn / xnT / inv_x come from launch_arcface_l2norm_t.  The partial buffers
+// follow arcface_fused_*_splits(Bp, Wp); sub [Bp] is the winning centre of each row's label class.
+int arcface_sub_rows(int C, int K);
+bool launch_arcface_sub_l2norm_t(const float* W, int C, int K, int D, int Dp, bf16* y, bf16* yT, float* inv,
+                                 float eps, hipStream_t st);
+bool launch_arcface_sub_fwd(const bf16* xn, const bf16* wn, const int64_t* labels, int B, int Bp, int C, int K,
+                            int Dp, float s, float m, int easy, float* lab, int* sub, float* part, float* loss,
+                            int* rank, float* lse, hipStream_t st);
+bool launch_arcface_sub_dx(const bf16* xn, const bf16* wn, const bf16* wnT, const int64_t* labels, int B, int Bp,
+                           int C, int K, int Dp, int D, float s, const float* lab, const int* sub, const float* lse,
+                           const float* gout, float scale, const float* inv_x, float* part, void* dx, bool dx_bf16,
+                           hipStream_t st);
+bool launch_arcface_sub_dw(const bf16* xn, const bf16* xnT, const bf16* wn, const int64_t* labels, int B, int Bp,
+                           int C, int K, int Dp, int D, float s, const float* lab, const int* sub, const float* lse,
+                           const float* gout, float scale, const float* inv_w, float* part, float* info, float* dw,
+                           hipStream_t st);
 // SyncBN peer-memory exchange (peer.hip): gather (mode 0, dst [world][n]) or rank-ordered sum
 // (mode 1, dst [n]) of n floats through the IPC-mapped mailboxes `boxes` ([world] base addresses);
 // a rank missing for timeout_ms sets *err and poisons dst with NaN (this and every later exchange)

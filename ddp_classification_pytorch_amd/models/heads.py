@@ -40,26 +40,46 @@ class MLPHead(nn.Module):
 
 
 class ArcMarginProduct(nn.Module):
-    """cos(theta + m) margin on the target class, scaled by s; weight [out, in] (xavier init)."""
+    """cos(theta + m) margin on the target class, scaled by s; weight [out, in] (xavier init).
 
-    def __init__(self, in_features=256, out_features=2173, s=30.0, m=0.50, easy_margin=True):
+    ``sub_centers`` = K > 1 is Sub-center ArcFace (Deng et al., ECCV 2020): weight [out, K, in]
+    (xavier init over the [out * K, in] rows), a sample scored against the nearest of a class's K
+    centres.  ``forward`` then keeps the winning centre of each row's label class in the
+    non-persistent buffer ``last_sub_idx`` (int32 [B])."""
+
+    def __init__(self, in_features=256, out_features=2173, s=30.0, m=0.50, easy_margin=True, sub_centers=1):
         super().__init__()
         self.in_features, self.out_features = in_features, out_features
         self.s, self.m, self.easy_margin = s, m, easy_margin
-        self.weight = nn.Parameter(torch.empty(out_features, in_features))
-        nn.init.xavier_uniform_(self.weight)
+        self.sub_centers = int(sub_centers)
+        if self.sub_centers == 1:
+            self.weight = nn.Parameter(torch.empty(out_features, in_features))
+            nn.init.xavier_uniform_(self.weight)
+        else:
+            Fn.arcface_sub_check(self.sub_centers, in_features)
+            w = torch.empty(out_features * self.sub_centers, in_features)
+            nn.init.xavier_uniform_(w)
+            self.weight = nn.Parameter(w.view(out_features, self.sub_centers, in_features))
+            self.register_buffer("last_sub_idx", torch.zeros(0, dtype=torch.int32), persistent=False)
         self.cos_m, self.sin_m = math.cos(m), math.sin(m)
         self.th, self.mm = math.cos(math.pi - m), math.sin(math.pi - m) * m
 
     def forward(self, x, label, return_logits=False):
         """-> (mean CE loss over margin logits, label rank, margin logits or empty)."""
-        return Fn.arcface_loss(x, self.weight, label, self.s, self.m, self.easy_margin, return_logits)
+        if self.sub_centers == 1:
+            return Fn.arcface_loss(x, self.weight, label, self.s, self.m, self.easy_margin, return_logits)
+        loss, rank, logits, self.last_sub_idx = Fn.arcface_loss(x, self.weight, label, self.s, self.m,
+                                                                self.easy_margin, return_logits, return_sub_idx=True)
+        return loss, rank, logits
 
     @torch.no_grad()
     def margin_logits(self, x, label):
-        """The reference's output tensor (ARCFACE/arc_main.py:157-176) in plain torch math."""
+        """The reference's output tensor (ARCFACE/arc_main.py:157-176) in plain torch math (with
+        sub-centres: the max over a class's K cosines first)."""
         cos = torch.nn.functional.linear(torch.nn.functional.normalize(x.float()),
-                                         torch.nn.functional.normalize(self.weight.float()))
+                                         torch.nn.functional.normalize(self.weight.float().flatten(0, -2)))
+        if self.sub_centers > 1:
+            cos = cos.view(-1, self.out_features, self.sub_centers).amax(2)
         sine = torch.sqrt((1.0 - cos.pow(2)).clamp(0, 1))
         phi = cos * self.cos_m - sine * self.sin_m
         phi = torch.where(cos > 0, phi, cos) if self.easy_margin else torch.where(cos > self.th, phi, cos - self.mm)

@@ -923,6 +923,32 @@ def arcface_bwd(cosv, labels, C, s, m, easy, dphi, grad_out, scale):
     return d.to(cosv.dtype)
 
 
+def arcface_sub_head(x, weight, labels, s, m, easy):
+    """Sub-center ArcFace (weight [C, K, D]) in plain fp32 torch math, differentiable in x and weight:
+    cosines to all K centres, the first maximum over K gathered (autograd routes the gradient to that
+    centre alone), the margin on the label class, cross-entropy rows.  A label outside [0, C) gives
+    loss 0 and no gradient.  -> (loss [B], rank [B], sub_idx [B] int32, margin logits [B, C])."""
+    C, Kc, _ = weight.shape
+    cm, sm, th, mm = _arc_consts(m)
+    cos = torch.einsum("bd,ckd->bck", F.normalize(_f(x), dim=1, eps=1e-12), F.normalize(_f(weight), dim=2, eps=1e-12))
+    cd = cos.detach()
+    first = torch.where(cd == cd.amax(2, keepdim=True), torch.arange(Kc), Kc).amin(2)  # smallest k of the maxima
+    cbar = cos.gather(2, first.unsqueeze(2)).squeeze(2)
+    valid = (labels >= 0) & (labels < C)
+    safe = labels.clamp(0, C - 1).view(-1, 1)
+    c = cbar.gather(1, safe).squeeze(1).clamp(-1, 1)
+    sn = torch.sqrt((1 - c * c).clamp(1e-12, 1))
+    p = c * cm - sn * sm
+    phi = torch.where(c > 0, p, c) if easy else torch.where(c > th, p, c - mm)
+    oh = torch.zeros_like(cbar).scatter_(1, safe, 1.0)
+    logits = s * (oh * phi.unsqueeze(1) + (1 - oh) * cbar)
+    t = s * phi
+    loss = (torch.logsumexp(logits, 1) - t) * valid
+    rank = ((logits > t.unsqueeze(1)) & (oh == 0)).sum(1).int()
+    sub = (first.gather(1, safe).squeeze(1) * valid).int()
+    return loss, rank, sub, logits
+
+
 def transpose2d(x):
     return x.t().contiguous()
 

@@ -1679,8 +1679,19 @@ def cross_entropy_rows(logits, labels, num_classes=None):
 @torch.no_grad()
 def arcface_rows(x, weight, labels, s=30.0, m=0.5, easy_margin=True, with_margin=True):
     """Per-sample (loss, rank) of the ArcFace head.  ``with_margin=False`` ranks the
-    plain scaled cosines (a label-free prediction)."""
+    plain scaled cosines (a label-free prediction).  A weight [C, K, D] (Sub-center ArcFace) runs the
+    fused sub-centre forward alone on the GPU: no [B, C K] matrix in evaluation either."""
     k = K(x)
+    if weight.dim() == 3:
+        # plain cosines: the margin kernel with m = 0 (phi = cos exactly)
+        mm, easy = (m, easy_margin) if with_margin else (0.0, True)
+        if not x.is_cuda:
+            loss, rank, _, _ = _ref.arcface_sub_head(x, weight, labels, float(s), float(mm), bool(easy))
+            return loss, rank
+        xn, _, _, wn, _, _ = _arcface_sub_operands(k, x, weight)
+        loss, rank, _, _, _ = k.arcface_sub_fwd(xn, wn, labels.to(torch.int64).contiguous(), x.shape[0],
+                                                weight.shape[0], weight.shape[1], float(s), float(mm), bool(easy))
+        return loss, rank
     C, D = weight.shape
     Dp = round_up(D, 8) if x.is_cuda else D
     Cp = round_up(C, 64) if x.is_cuda else C
@@ -1831,10 +1842,96 @@ def arcface_fused_supported(B: int, D: int) -> bool:
     return 1 <= D <= ARCFACE_FUSED_MAX_D
 
 
-def arcface_loss(x, weight, labels, s=30.0, m=0.5, easy_margin=True, return_logits=False):
+ARCFACE_SUB_MAX_K = 4
+ARCFACE_SUB_MAX_D = 256
+
+
+def arcface_sub_check(K: int, D: int) -> int:
+    """The limits of the fused Sub-center ArcFace head (csrc/arcface_sub.hip): 2..4 centres per class,
+    1 <= D <= 256.  Outside them a ValueError names the limit (there is no other path for K > 1 on
+    the GPU).  -> the padded width Dp."""
+    if not 2 <= K <= ARCFACE_SUB_MAX_K:
+        raise ValueError(f"the fused Sub-center ArcFace head covers 2 <= sub_centers <= {ARCFACE_SUB_MAX_K}, got {K}")
+    if not 1 <= D <= ARCFACE_SUB_MAX_D:
+        raise ValueError(f"the fused Sub-center ArcFace head covers 1 <= D <= {ARCFACE_SUB_MAX_D}, got D = {D}")
+    return 128 if D <= 128 else 256
+
+
+def _arcface_sub_operands(k, x, weight):
+    """-> (xn, xnT, inv_x, wn, wnT, inv_w): the normalised bf16 operands, the centres in the kernels'
+    sub-centre-planar row order."""
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16) or weight.dtype != torch.float32:
+        raise ValueError("the fused Sub-center ArcFace head takes fp32 or bf16 features [B, D] and an fp32 weight "
+                         f"[C, K, D], got {x.dtype} {tuple(x.shape)} and {weight.dtype} {tuple(weight.shape)}")
+    C, Kc, D = weight.shape
+    Dp = arcface_sub_check(Kc, D)
+    xn, xnT, inv_x = k.arcface_l2norm_t(x.contiguous(), round_up(x.shape[0], 64), Dp, 1e-12)
+    wn, wnT, inv_w = k.arcface_sub_l2norm_t(weight.detach().contiguous(), Dp, 1e-12)
+    return xn, xnT, inv_x, wn, wnT, inv_w
+
+
+class _ArcFaceSubFused(Function):
+    """Sub-center ArcFace (K centres per class, weight [C, K, D]) on csrc/arcface_sub.hip: the cosine
+    tiles, their max over K and the routing of dcos to the winning centre stay in MFMA registers --
+    no [B, C K] tensor.  -> (mean loss, label rank, sub_idx [B]: the winning centre of the label class)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, labels, s, m, easy):
+        k = K(x)
+        B, D = x.shape
+        C, Kc = weight.shape[:2]
+        xn, xnT, inv_x, wn, wnT, inv_w = _arcface_sub_operands(k, x, weight)
+        lab64 = labels.to(torch.int64).contiguous()
+        loss_rows, rank, lse, lab, sub = k.arcface_sub_fwd(xn, wn, lab64, B, C, Kc, s, m, easy)
+        ctx.save_for_backward(xn, xnT, inv_x, wn, wnT, inv_w, lab64, lse, lab, sub)
+        ctx.cfg = (B, C, Kc, D, s, x.dtype == torch.bfloat16)
+        sub_idx = sub[:B]
+        ctx.mark_non_differentiable(rank, sub_idx)
+        ctx.set_materialize_grads(False)
+        return loss_rows.mean(), rank, sub_idx
+
+    @staticmethod
+    def backward(ctx, g, _grank, _gsub):
+        if g is None:
+            return (None,) * 6
+        xn, xnT, inv_x, wn, wnT, inv_w, lab64, lse, lab, sub = ctx.saved_tensors
+        B, C, Kc, D, s, x_bf16 = ctx.cfg
+        k = K(xn)
+        g = g.reshape(1)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = k.arcface_sub_dx(xn, wn, wnT, lab64, lse, lab, sub, g, 1.0 / B, inv_x, B, C, Kc, D, s, x_bf16)
+        if ctx.needs_input_grad[1]:
+            dw = k.arcface_sub_dw(xn, xnT, wn, lab64, lse, lab, sub, g, 1.0 / B, inv_w, B, C, Kc, D, s)
+        return dx, dw, None, None, None, None
+
+
+def _arcface_sub_loss(x, weight, labels, s, m, easy_margin, return_logits):
+    """-> (mean loss, rank, logits or empty, sub_idx) for a weight [C, K, D]."""
+    if x.is_cuda:
+        if return_logits:
+            raise ValueError("the fused Sub-center ArcFace head writes no logits (return_logits needs a 2-D weight; "
+                             "ArcMarginProduct.margin_logits gives them in torch math)")
+        loss, rank, sub = _ArcFaceSubFused.apply(x, weight, labels, float(s), float(m), bool(easy_margin))
+        return loss, rank, torch.empty(0, device=x.device), sub
+    loss_rows, rank, sub, logits = _ref.arcface_sub_head(x, weight, labels, float(s), float(m), bool(easy_margin))
+    return loss_rows.mean(), rank, (logits.detach() if return_logits else torch.empty(0)), sub
+
+
+def arcface_loss(x, weight, labels, s=30.0, m=0.5, easy_margin=True, return_logits=False, return_sub_idx=False):
     """Returns (mean loss, rank of label, margin logits or empty).  On the GPU without
     ``return_logits`` (training, the reference's loss) the fused head runs for every D <= 512 and
-    every batch size: no [B, C] tensor (wider features take the unfused kernel path)."""
+    every batch size: no [B, C] tensor (wider features take the unfused kernel path).
+
+    A 3-D ``weight`` [C, K, D] is Sub-center ArcFace (K centres per class, the nearest one scores):
+    the fused sub-centre head on the GPU (:func:`arcface_sub_check` names its limits), plain torch
+    math on the CPU.  ``return_sub_idx`` appends the winning centre of each row's label class
+    (int32 [B]; 3-D weights only)."""
+    if weight.dim() == 3:
+        out = _arcface_sub_loss(x, weight, labels, s, m, easy_margin, return_logits)
+        return out if return_sub_idx else out[:3]
+    if return_sub_idx:
+        raise ValueError("return_sub_idx needs a weight [C, K, D]")
     if (x.is_cuda and not return_logits and x.dim() == 2 and arcface_fused_supported(x.shape[0], x.shape[1])
             and arcface_fused_enabled() and x.dtype in (torch.float32, torch.bfloat16)):
         loss, rank = _ArcFaceFused.apply(x, weight, labels, float(s), float(m), bool(easy_margin))
