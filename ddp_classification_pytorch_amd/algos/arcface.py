@@ -10,14 +10,16 @@ one DDP wrapper (one bucketed all-reduce stream, same math).
 
 Eval: the reference applies the margin with the TRUE labels at validation
 (ARCFACE/arc_main.py:368); that is the default (``--arc-eval-with-labels``),
-``--arc-eval-plain-cosine`` ranks plain cosines instead.
+``--arc-eval-plain-cosine`` ranks plain cosines instead.  ``--arc-eval-knn K`` adds the
+label-free retrieval evaluation (engine/loop.py ``evaluate_knn``): Recall@1 / @3 / @K of every
+validation embedding against the other validation embeddings.
 """
 from __future__ import annotations
 
 import torch.nn as nn
 
 from ..engine.loop import ClassificationLoop
-from ..config import refuse_mix
+from ..config import check_knn, refuse_mix
 from ..engine.runtime import build_data, setup
 from ..models import build_model
 from ..models.heads import ArcMarginProduct, MLPHead
@@ -53,6 +55,7 @@ def build_arcface(args):
 
 def run(args):
     refuse_mix(args, "arcface")
+    check_knn(args)
     rt = setup(args)
     train_data, val_data, _, _ = build_data(args, rt)
     model = build_arcface(args).to(rt.device)
@@ -76,5 +79,6 @@ def run(args):
     models = {"model": model}
     # --model-ema: over every model of the dict (backbone, embedding head and the ArcFace class centres)
     loop = ClassificationLoop(args, rt, models, opt, sched, train_data, val_data, fwd_train, fwd_eval,
-                              train_modules=[net], ema=build_ema(args, models, opt))
+                              train_modules=[net], ema=build_ema(args, models, opt),
+                              embed_eval=lambda batch: model.features(batch[0]))
     return loop.run()

@@ -36,6 +36,9 @@ def build_classifier(args, log_softmax=False):
 
 
 def run(args):
+    from ..config import refuse_knn
+
+    refuse_knn(args, "baseline")
     rt = setup(args)
     train_data, val_data, _, _ = build_data(args, rt)
     model = build_classifier(args).to(rt.device)

@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from ..engine.logger import MetricsLogger
 from ..engine.loop import ClassificationLoop
-from ..config import refuse_ema, refuse_mix
+from ..config import refuse_ema, refuse_knn, refuse_mix
 from ..engine.runtime import build_data, setup
 from ..ops import functional as Fn
 from ..optim import FusedSGD
@@ -155,6 +155,7 @@ def run(args):
     visible immediately (persistent loader workers hold stale dataset copies)."""
     refuse_mix(args, "plc")
     refuse_ema(args, "plc")
+    refuse_knn(args, "plc")
     from .baseline import build_classifier
 
     rt = setup(args)

@@ -50,7 +50,9 @@ COMMON_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-D__HIP_PLATFORM_AMD__=1", "-DUSE
 # SLP vectorizer forms from adjacent scalar adds / FMAs) issues slower than scalar fp32
 FILE_FLAGS = {"stem.hip": ["-fno-slp-vectorize"],
               # the sub-centre head's softmax tail sits between two MFMA groups: scalar fp32 there too
-              "arcface_sub.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "arcface_sub.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the top-k selection's compares and selects run beside the MFMAs as well
+              "knn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _headers():

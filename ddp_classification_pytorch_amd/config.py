@@ -180,6 +180,9 @@ def build_parser() -> argparse.ArgumentParser:
     a("--arc-eval-with-labels", action="store_true", default=True,
       help="reference behaviour: margin applied with true labels at eval (ARCFACE/arc_main.py:368)")
     a("--arc-eval-plain-cosine", dest="arc_eval_with_labels", action="store_false")
+    a("--arc-eval-knn", type=int, default=0,
+      help="retrieval evaluation after each validation: every validation sample's K (1..8) nearest other "
+           "validation samples by cosine, Recall@1 / @3 / @K in val_knn records (0: off)")
     a("--arc-sub-centers", type=int, default=1,
       help="Sub-center ArcFace: K centres per class, a sample scored against the nearest one (1: plain ArcFace; "
            "the fused head covers 2..4 at an embedding width <= 256)")
@@ -273,6 +276,20 @@ def refuse_ema(args, workload: str):
     if given:
         raise ValueError(f"{', '.join(given)}: the weight EMA is wired for the baseline, arcface and cdr workloads; "
                          f"the {workload} workload runs its own loop")
+
+
+def refuse_knn(args, workload: str):
+    """Every workload but arcface calls this at start-up: --arc-eval-knn there is an error, never
+    silently ignored."""
+    if int(getattr(args, "arc_eval_knn", 0) or 0):
+        raise ValueError(f"--arc-eval-knn: the retrieval evaluation is wired for --workload arcface only; the "
+                         f"{workload} workload has no embedding head")
+
+
+def check_knn(args):
+    k = int(getattr(args, "arc_eval_knn", 0) or 0)
+    if not 0 <= k <= 8:
+        raise ValueError(f"--arc-eval-knn covers 1 <= K <= 8 (0: off), got {k}")
 
 
 def _cuda_available() -> bool:

@@ -2196,6 +2196,64 @@ Tensor arcface_sub_dw(const Tensor& xn, const Tensor& xnT, const Tensor& wn, con
   return dw;
 }
 
+// Fused top-k retrieval (knn.hip).  x [R][D] fp32 / bf16 -> bf16 operand rows [Rp][Dp] (zero padding),
+// L2-normalised or just converted
+Tensor knn_prep(const Tensor& x, int64_t Rp, int64_t Dp, bool normalize, double eps) {
+  CHECK_DEV(x);
+  CHECK_CONTIG(x);
+  TORCH_CHECK(x.dim() == 2 && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
+              "knn_prep: x [R][D] fp32 or bf16");
+  auto y = at::empty({Rp, Dp}, x.options().dtype(at::kBFloat16));
+  TORCH_CHECK(dcp::launch_knn_prep(x.data_ptr(), x.scalar_type() == at::kBFloat16, x.size(0), x.size(1), (int)Rp,
+                                   (int)Dp, normalize, bpm(y), (float)eps, cur_stream()),
+              "knn_prep: Rp % 64, D <= Dp in {128, 256, 512}");
+  return y;
+}
+
+int64_t knn_splits(int64_t Nqp, int64_t Ngp) { return dcp::knn_splits((int)Nqp, (int)Ngp); }
+
+// qn [Nqp][Dp], gn [Ngp][Dp] from knn_prep -> (val [Nq][k] fp32, idx [Nq][k] int32, first_hit [Nq] int32
+// -- empty without labels).  exclude int32 [Nq]; q_labels [Nq] / g_labels [Ng] int64.
+std::tuple<Tensor, Tensor, Tensor> knn_topk(const Tensor& qn, const Tensor& gn, int64_t Nq, int64_t Ng, int64_t k,
+                                            int64_t splits, const optional<Tensor>& exclude,
+                                            const optional<Tensor>& q_labels, const optional<Tensor>& g_labels) {
+  CHECK_ACT(qn);
+  CHECK_ACT(gn);
+  const int Nqp = qn.size(0), Ngp = gn.size(0), Dp = qn.size(1);
+  TORCH_CHECK(gn.size(1) == Dp && Nq >= 1 && Nq <= Nqp && Ng >= 1 && Ng <= Ngp, "knn_topk shapes");
+  TORCH_CHECK(k >= 1 && k <= 8, "knn_topk: 1 <= k <= 8, got ", k);
+  TORCH_CHECK(splits >= 1 && splits <= 64, "knn_topk: 1 <= splits <= 64, got ", splits);
+  TORCH_CHECK(q_labels.has_value() == g_labels.has_value(), "knn_topk: q_labels and g_labels come together");
+  const int* ex = nullptr;
+  if (exclude.has_value()) {
+    TORCH_CHECK(exclude->is_cuda() && exclude->scalar_type() == at::kInt && exclude->is_contiguous() &&
+                    exclude->numel() == Nq,
+                "knn_topk: exclude int32 [Nq]");
+    ex = exclude->data_ptr<int>();
+  }
+  const int64_t *ql = nullptr, *gl = nullptr;
+  if (q_labels.has_value()) {
+    TORCH_CHECK(q_labels->is_cuda() && g_labels->is_cuda() && q_labels->scalar_type() == at::kLong &&
+                    g_labels->scalar_type() == at::kLong && q_labels->is_contiguous() && g_labels->is_contiguous() &&
+                    q_labels->numel() == Nq && g_labels->numel() == Ng,
+                "knn_topk: labels int64 [Nq] and [Ng]");
+    ql = q_labels->data_ptr<int64_t>();
+    gl = g_labels->data_ptr<int64_t>();
+  }
+  const int64_t kmax = dcp::knn_kmax((int)k);
+  auto iopt = qn.options().dtype(at::kInt);
+  auto pval = at::empty({splits * Nqp * kmax}, f32_like(qn));
+  auto pidx = at::empty({splits * Nqp * kmax}, iopt);
+  auto val = at::empty({Nq, k}, f32_like(qn));
+  auto idx = at::empty({Nq, k}, iopt);
+  auto hit = at::empty({ql ? Nq : 0}, iopt);
+  TORCH_CHECK(dcp::launch_knn_topk(bp(qn), bp(gn), (int)Nq, Nqp, (int)Ng, Ngp, Dp, (int)k, (int)splits, ex, ql, gl,
+                                   pval.data_ptr<float>(), pidx.data_ptr<int>(), val.data_ptr<float>(),
+                                   idx.data_ptr<int>(), ql ? hit.data_ptr<int>() : nullptr, cur_stream()),
+              "knn_topk: unsupported shape (rows padded to 64, D padded to 128 / 256 / 512, k <= 8)");
+  return {val, idx, hit};
+}
+
 // ---------------------------------------------------------------------------
 // optimizers (multi-tensor). table: int64 [n,6] = (p, g, s1, s2, shadow, numel); chunks int32 [k,2]
 // ---------------------------------------------------------------------------
@@ -2658,6 +2716,10 @@ TORCH_LIBRARY(dcp, m) {
         "float scale, Tensor inv_x, int B, int C, int D, float s, bool out_bf16) -> Tensor", &arcface_fused_dx);
   m.def("arcface_fused_dw(Tensor xn, Tensor xnT, Tensor wn, Tensor labels, Tensor lse, Tensor lab, Tensor grad_out, "
         "float scale, Tensor inv_w, int B, int C, int D, float s) -> Tensor", &arcface_fused_dw);
+  m.def("knn_prep(Tensor x, int Rp, int Dp, bool normalize, float eps) -> Tensor", &knn_prep);
+  m.def("knn_splits(int Nqp, int Ngp) -> int", &knn_splits);
+  m.def("knn_topk(Tensor qn, Tensor gn, int Nq, int Ng, int k, int splits, Tensor? exclude, Tensor? q_labels, "
+        "Tensor? g_labels) -> (Tensor, Tensor, Tensor)", &knn_topk);
   m.def("arcface_sub_l2norm_t(Tensor w, int Dp, float eps) -> (Tensor, Tensor, Tensor)", &arcface_sub_l2norm_t);
   m.def("arcface_sub_fwd(Tensor xn, Tensor wn, Tensor labels, int B, int C, int K, float s, float m, bool easy) -> "
         "(Tensor, Tensor, Tensor, Tensor, Tensor)", &arcface_sub_fwd);

@@ -491,6 +491,19 @@ bool launch_arcface_sub_dw(const bf16* xn, const bf16* xnT, const bf16* wn, cons
                            int C, int K, int Dp, int D, float s, const float* lab, const int* sub, const float* lse,
                            const float* gout, float scale, const float* inv_w, float* part, float* info, float* dw,
                            hipStream_t st);
+// Fused top-k retrieval (knn.hip): no [Nq, Ng] tensor.  qn [Nqp][Dp] / gn [Ngp][Dp] bf16 operands from
+// launch_knn_prep (zero padding rows), Nqp % 64 == Ngp % 64 == 0, Dp in {128, 256, 512}, 1 <= k <= 8,
+// 1 <= S <= 64 gallery splits (knn_splits: the heuristic); false = unsupported.  Order: score descending,
+// then gallery index ascending; exclude [Nq] (or null) names one gallery row per query that is never
+// returned.  pval / pidx [S][Nqp][knn_kmax(k)] are the split partials; val / idx [Nq][k]; with both label
+// arrays first_hit [Nq] = position of the first neighbour carrying the query's label (k: none).
+bool launch_knn_prep(const void* x, bool is_bf16, int R, int D, int Rp, int Dp, bool normalize, bf16* y, float eps,
+                     hipStream_t st);
+int knn_kmax(int k);
+int knn_splits(int Nqp, int Ngp);
+bool launch_knn_topk(const bf16* qn, const bf16* gn, int Nq, int Nqp, int Ng, int Ngp, int Dp, int k, int S,
+                     const int* exclude, const int64_t* q_labels, const int64_t* g_labels, float* pval, int* pidx,
+                     float* val, int* idx, int* first_hit, hipStream_t st);
 // SyncBN peer-memory exchange (peer.hip): gather (mode 0, dst [world][n]) or rank-ordered sum
 // (mode 1, dst [n]) of n floats through the IPC-mapped mailboxes `boxes` ([world] base addresses);
 // a rank missing for timeout_ms sets *err and poisons dst with NaN (this and every later exchange)

@@ -29,7 +29,11 @@ Differences from the reference, all deliberate:
 * ``--model-ema``: an exponential moving average of the weights (optim/ema.py) updated inside the
   step -- and so inside the captured HIP graph --, evaluated after the live model under
   ``ema.applied()`` (``val_ema`` records, ``VAL-EMA`` lines) and carried by the checkpoints;
-  ``best.pth`` is still chosen by the live model's top-1.
+  ``best.pth`` is still chosen by the live model's top-1;
+* ``--arc-eval-knn K`` (ArcFace): after each validation the validation set is embedded once more
+  and every sample retrieves its K nearest other validation samples (``Fn.cosine_topk``, the gallery
+  all-gathered over the ranks); Recall@1 / @3 / @K go to ``val_knn`` records and ``VAL-KNN`` lines
+  (under ``--model-ema`` also for the averaged weights, ``ema=True``).  ``best.pth`` stays with top-1.
 """
 from __future__ import annotations
 
@@ -72,19 +76,63 @@ def valid_count(sampler, n_total):
     return max(0, math.ceil((sampler.n - sampler.rank) / sampler.world))
 
 
+@torch.no_grad()
+def knn_counts(feats, labels, k):
+    """Leave-one-out retrieval counts of this rank's rows against the gallery of ALL ranks' rows.
+
+    ``feats`` [n, D] / ``labels`` [n] are the rank's valid rows (n may differ between ranks, and be 0).
+    World size > 1: equal-size padded buffers and the row counts are all-gathered, the gallery is rank
+    0's rows, then rank 1's, ...; every row is excluded at its own position there.  -> fp64 [4] on the
+    device: (#first_hit < k, #first_hit < 1, #first_hit < 3, n), this rank's share (sum over the ranks
+    with ``_allreduce``)."""
+    dev, n = feats.device, feats.shape[0]
+    labels = labels.reshape(-1).to(torch.int64)
+    gallery, glabels, off = feats, labels, 0
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        world, rank = dist.get_world_size(), dist.get_rank()
+        host = dist.get_backend() == "gloo"  # gloo moves host tensors only
+        cdev = torch.device("cpu") if host else dev
+        mine = torch.tensor([n, feats.shape[1]], dtype=torch.int64, device=cdev)
+        sizes = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(sizes, mine)
+        counts = [int(t[0]) for t in sizes]
+        m, D = max(max(counts), 1), max(int(t[1]) for t in sizes)
+        fbuf = torch.zeros(m, D, dtype=torch.float32, device=cdev)
+        ybuf = torch.zeros(m, dtype=torch.int64, device=cdev)
+        fbuf[:n], ybuf[:n] = feats.float().to(cdev), labels.to(cdev)
+        fall = [torch.empty_like(fbuf) for _ in range(world)]
+        yall = [torch.empty_like(ybuf) for _ in range(world)]
+        dist.all_gather(fall, fbuf)
+        dist.all_gather(yall, ybuf)
+        gallery = torch.cat([f[:c] for f, c in zip(fall, counts)]).to(dev)
+        glabels = torch.cat([y[:c] for y, c in zip(yall, counts)]).to(dev)
+        off = sum(counts[:rank])
+        feats = fbuf[:n].to(dev)  # the same fp32 rows the gallery holds
+    acc = torch.zeros(4, dtype=torch.float64, device=dev)
+    if n:
+        own = torch.arange(off, off + n, dtype=torch.int32, device=dev)
+        _, _, hit = Fn.cosine_topk(feats, gallery, k, exclude=own, q_labels=labels, g_labels=glabels)
+        Fn.metric_accum(acc, (hit < k).float(), 1.0, hit, n)
+    return acc
+
+
 class ClassificationLoop:
     """``forward_train(batch) -> (loss, rank)``; ``forward_eval(batch) -> (loss_rows, rank)``;
     optional ``post_backward()`` (e.g. CDR gradient masking) and ``epoch_hook(epoch)``."""
 
     def __init__(self, args, rt, models: dict, optimizer, scheduler, train_data, val_data, forward_train,
                  forward_eval, post_backward=None, logger: MetricsLogger = None, scheduler_before_epoch=False,
-                 train_modules=None, ema=None):
+                 train_modules=None, ema=None, embed_eval=None):
         self.args, self.rt = args, rt
         self.models, self.optimizer, self.scheduler = models, optimizer, scheduler
         self.train_data, self.val_data = train_data, val_data
         self.forward_train, self.forward_eval = forward_train, forward_eval
         self.post_backward = post_backward
         self.ema = ema  # optim.WeightEMA or None (--model-ema)
+        # --arc-eval-knn K: ``embed_eval(batch) -> [B, D]`` embeddings for the retrieval evaluation
+        self.embed_eval, self.knn_k = embed_eval, int(getattr(args, "arc_eval_knn", 0) or 0)
+        if self.knn_k and embed_eval is None:
+            raise ValueError("--arc-eval-knn needs a workload that provides embeddings (arcface)")
         self.logger = logger or MetricsLogger(args.out_dir if rt.is_main else None)
         self.scheduler_before_epoch = scheduler_before_epoch  # CDR steps its scheduler before training (:365-366)
         self.train_modules = train_modules or list(models.values())
@@ -330,6 +378,38 @@ class ClassificationLoop:
         n = max(tot[3], 1)
         return {"loss": tot[0] / n, "top1": tot[1] / n, "top3": tot[2] / n, "count": tot[3]}
 
+    @torch.no_grad()
+    def evaluate_knn(self):
+        """Retrieval Recall@1 / @3 / @K of the validation set against itself (each sample's own row
+        excluded), over the sampler's valid rows of every rank."""
+        for m in self.train_modules:
+            m.eval()
+        left = valid_count(getattr(self.val_data, "sampler", None), float("inf"))
+        fs, ys = [], []
+        for batch in self.val_data:
+            f = self.embed_eval(batch)
+            k = int(min(f.shape[0], left))
+            left -= k
+            if k > 0:
+                fs.append(f[:k])
+                ys.append(batch[1][:k])
+        if not fs:  # a rank without valid rows still takes part in the gathering
+            fs, ys = [torch.zeros(0, 1, device=self.rt.device)], [torch.zeros(0, dtype=torch.int64, device=self.rt.device)]
+        tot = _allreduce(knn_counts(torch.cat(fs), torch.cat(ys), self.knn_k)).tolist()
+        n = max(tot[3], 1)
+        out = {"k": self.knn_k, "recall1": tot[1] / n}
+        if self.knn_k >= 3:
+            out["recall3"] = tot[2] / n
+        out.update(recallK=tot[0] / n, n=tot[3])
+        return out
+
+    def _log_knn(self, epoch, tag, **extra):
+        kn = self.evaluate_knn()
+        self.logger.log("val_knn", epoch=epoch, **kn, **extra)
+        ks = [(1, "recall1")] + ([(3, "recall3")] if self.knn_k > 3 else []) + ([(self.knn_k, "recallK")] if self.knn_k > 1 else [])
+        self.logger.line(f"{tag} Epoch {epoch + 1}: " + " ".join(f"recall@{k} {100 * kn[key]:.3f}" for k, key in ks) +
+                         f" (n={int(kn['n'])})")
+
     def run(self):
         a = self.args
         self.maybe_resume()
@@ -345,6 +425,8 @@ class ClassificationLoop:
                 self.logger.line(f"VAL Epoch {epoch + 1}: loss {va['loss']:.4f} top1 {100 * va['top1']:.3f} "
                                  f"top3 {100 * va['top3']:.3f} (n={int(va['count'])}) | train loss {tr['loss']:.4f} "
                                  f"top1 {100 * tr['top1']:.3f} ({tr['time']:.1f}s)")
+                if self.knn_k:
+                    self._log_knn(epoch, "VAL-KNN")
                 if self.ema is not None:
                     with self.ema.applied():  # the live model computes on the averages; every bit comes back
                         ve = self.evaluate()
@@ -352,6 +434,9 @@ class ClassificationLoop:
                     self.logger.line(f"VAL-EMA Epoch {epoch + 1}: loss {ve['loss']:.4f} top1 {100 * ve['top1']:.3f} "
                                      f"top3 {100 * ve['top3']:.3f} (n={int(ve['count'])}, "
                                      f"{self.ema.num_updates} updates)")
+                    if self.knn_k:
+                        with self.ema.applied():
+                            self._log_knn(epoch, "VAL-KNN-EMA", ema=True)
             if self.scheduler is not None and not self.scheduler_before_epoch:
                 self.scheduler.step()
             if (epoch + 1) % a.save_every == 0 or epoch + 1 == a.epochs:

@@ -949,6 +949,38 @@ def arcface_sub_head(x, weight, labels, s, m, easy):
     return loss, rank, sub, logits
 
 
+def knn_prep(x, Rp, Dp, normalize, eps):
+    xf = F.normalize(_f(x), dim=1, eps=eps) if normalize else _f(x)
+    return F.pad(xf, (0, Dp - x.shape[1], 0, Rp - x.shape[0])).bfloat16()
+
+
+def cosine_topk(q, g, k, normalize, exclude, q_labels, g_labels):
+    """Reference math of the fused retrieval (csrc/knn.hip): operands rounded to bf16 (after the fp32
+    L2 normalisation when ``normalize``), fp32 scores, a stable descending sort (score descending, then
+    gallery index ascending); the excluded column and NaN scores are no candidates, the tail past the
+    candidates is (-inf, -1).  -> (val [Nq, k], idx [Nq, k] int32, first_hit [Nq] int32 or None)."""
+    qf, gf = _f(q), _f(g)
+    if normalize:
+        qf, gf = F.normalize(qf, dim=1, eps=1e-12), F.normalize(gf, dim=1, eps=1e-12)
+    s = qf.bfloat16().float() @ gf.bfloat16().float().t()
+    s = torch.where(torch.isnan(s), torch.full_like(s, -math.inf), s)
+    if exclude is not None:
+        cols = torch.arange(s.shape[1]).unsqueeze(0)
+        s = s.masked_fill(cols == exclude.view(-1, 1).long(), -math.inf)
+    val, idx = torch.sort(s, dim=1, descending=True, stable=True)
+    pad = k - min(k, s.shape[1])
+    val, idx = val[:, :k], idx[:, :k].int()
+    if pad:
+        val = torch.cat([val, val.new_full((val.shape[0], pad), -math.inf)], 1)
+        idx = torch.cat([idx, idx.new_full((idx.shape[0], pad), -1)], 1)
+    idx = torch.where(val == -math.inf, torch.full_like(idx, -1), idx)
+    hit = None
+    if q_labels is not None:
+        same = (g_labels.long()[idx.clamp(min=0).long()] == q_labels.long().view(-1, 1)) & (idx >= 0)
+        hit = torch.where(same, torch.arange(k), k).amin(1).int()
+    return val, idx, hit
+
+
 def transpose2d(x):
     return x.t().contiguous()
 

@@ -1939,6 +1939,72 @@ def arcface_loss(x, weight, labels, s=30.0, m=0.5, easy_margin=True, return_logi
     return _ArcFace.apply(x, weight, labels, float(s), float(m), bool(easy_margin), bool(return_logits))
 
 
+# ----------------------------------------------------------------------------- retrieval
+KNN_MAX_K = 8
+KNN_MAX_D = 512
+
+
+def _knn_check(x, name):
+    if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16) or x.shape[0] < 1:
+        raise ValueError(f"cosine_topk takes fp32 or bf16 rows [N, D], got {name} {x.dtype} {tuple(x.shape)}")
+    if not 1 <= x.shape[1] <= KNN_MAX_D:
+        raise ValueError(f"cosine_topk covers 1 <= D <= {KNN_MAX_D}, got D = {x.shape[1]}")
+
+
+@torch.no_grad()
+def knn_operand(x, normalize=True):
+    """The bf16 operand rows [round_up(N, 64), Dp] of :func:`cosine_topk` on the GPU (csrc/knn.hip):
+    L2-normalised as the fused ArcFace heads normalise, or just converted; zero padding."""
+    _knn_check(x, "x")
+    return K(x).knn_prep(x.detach().contiguous(), round_up(x.shape[0], 64), arcface_fused_dp(x.shape[1]),
+                         bool(normalize), 1e-12)
+
+
+@torch.no_grad()
+def cosine_topk(q, g, k, normalize=True, exclude=None, q_labels=None, g_labels=None, splits=None):
+    """For every row of ``q`` [Nq, D] the ``k`` (1..8) rows of ``g`` [Ng, D] of largest cosine
+    (``normalize=False``: raw dot product), D <= 512.  -> (val fp32 [Nq, k], idx int32 [Nq, k]), plus
+    first_hit int32 [Nq] when both label tensors are given.
+
+    Order: score descending, then gallery index ascending.  ``exclude`` (int [Nq], -1 = none) names a
+    gallery row a query never returns (its own position when the gallery holds the queries); NaN
+    scores are no candidates; with fewer than k candidates the tail is (-inf, -1).  ``first_hit`` is
+    the position of the first neighbour whose label equals the query's (k if none) -- the ``rank``
+    of :func:`metric_accum`, so ``first_hit == 0`` counts as Recall@1 and ``first_hit < 3`` as Recall@3.
+
+    On the GPU the fused kernels of csrc/knn.hip: bf16 operands, fp32 MFMA scores consumed in registers,
+    nothing [Nq, Ng] written; ``splits`` (1..64, default a heuristic) is the number of gallery splits and
+    does not change a bit of the result.  On the CPU the reference math of ``_ref.cosine_topk``."""
+    _knn_check(q, "q")
+    _knn_check(g, "g")
+    k = int(k)
+    if q.shape[1] != g.shape[1] or q.device != g.device:
+        raise ValueError(f"cosine_topk: q {tuple(q.shape)} on {q.device} and g {tuple(g.shape)} on {g.device}")
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"cosine_topk covers 1 <= k <= {KNN_MAX_K}, got k = {k}")
+    if (q_labels is None) != (g_labels is None):
+        raise ValueError("cosine_topk: q_labels and g_labels come together")
+    Nq, Ng = q.shape[0], g.shape[0]
+    if exclude is not None and exclude.numel() != Nq:
+        raise ValueError(f"cosine_topk: exclude holds {exclude.numel()} entries for {Nq} queries")
+    if q_labels is not None and (q_labels.numel() != Nq or g_labels.numel() != Ng):
+        raise ValueError("cosine_topk: one label per query row and per gallery row")
+    if not q.is_cuda:
+        val, idx, hit = _ref.cosine_topk(q, g, k, bool(normalize), exclude, q_labels, g_labels)
+        return (val, idx) if hit is None else (val, idx, hit)
+    ops = K(q)
+    qn = knn_operand(q, normalize)
+    gn = qn if g is q else knn_operand(g, normalize)
+    S = int(splits) if splits is not None else ops.knn_splits(qn.shape[0], gn.shape[0])
+    if not 1 <= S <= 64:
+        raise ValueError(f"cosine_topk: 1 <= splits <= 64, got {S}")
+    ex = None if exclude is None else exclude.to(device=q.device, dtype=torch.int32).contiguous()
+    ql = None if q_labels is None else q_labels.to(device=q.device, dtype=torch.int64).contiguous()
+    gl = None if g_labels is None else g_labels.to(device=q.device, dtype=torch.int64).contiguous()
+    val, idx, hit = ops.knn_topk(qn, gn, Nq, Ng, k, S, ex, ql, gl)
+    return (val, idx) if ql is None else (val, idx, hit)
+
+
 # ----------------------------------------------------------------------------- misc
 def s2d_block(s2d) -> int:
     """The space-to-depth block of an input-layout ``s2d`` value: False / 0 none, True / 2 the
