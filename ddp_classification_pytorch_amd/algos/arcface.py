@@ -12,7 +12,9 @@ Eval: the reference applies the margin with the TRUE labels at validation
 (ARCFACE/arc_main.py:368); that is the default (``--arc-eval-with-labels``),
 ``--arc-eval-plain-cosine`` ranks plain cosines instead.  ``--arc-eval-knn K`` adds the
 label-free retrieval evaluation (engine/loop.py ``evaluate_knn``): Recall@1 / @3 / @K of every
-validation embedding against the other validation embeddings.
+validation embedding against the other validation embeddings.  ``--arc-eval-knn-vote K`` (K <= 256,
+``--arc-knn-temperature``) classifies every validation embedding by the weighted vote of its K nearest
+other validation embeddings (``evaluate_knn_vote``).
 """
 from __future__ import annotations
 

@@ -52,7 +52,8 @@ FILE_FLAGS = {"stem.hip": ["-fno-slp-vectorize"],
               # the sub-centre head's softmax tail sits between two MFMA groups: scalar fp32 there too
               "arcface_sub.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the top-k selection's compares and selects run beside the MFMAs as well
-              "knn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "knn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              "knn_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _headers():

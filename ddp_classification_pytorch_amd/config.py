@@ -183,6 +183,11 @@ def build_parser() -> argparse.ArgumentParser:
     a("--arc-eval-knn", type=int, default=0,
       help="retrieval evaluation after each validation: every validation sample's K (1..8) nearest other "
            "validation samples by cosine, Recall@1 / @3 / @K in val_knn records (0: off)")
+    a("--arc-eval-knn-vote", type=int, default=0,
+      help="weighted kNN classification after each validation: every validation sample is classified by its K "
+           "(1..256) nearest other validation samples, weights exp(cos / T); top1 and the mean agreement with "
+           "its own label in val_knn_vote records (0: off)")
+    a("--arc-knn-temperature", type=float, default=0.07, help="T of --arc-eval-knn-vote")
     a("--arc-sub-centers", type=int, default=1,
       help="Sub-center ArcFace: K centres per class, a sample scored against the nearest one (1: plain ArcFace; "
            "the fused head covers 2..4 at an embedding width <= 256)")
@@ -284,12 +289,20 @@ def refuse_knn(args, workload: str):
     if int(getattr(args, "arc_eval_knn", 0) or 0):
         raise ValueError(f"--arc-eval-knn: the retrieval evaluation is wired for --workload arcface only; the "
                          f"{workload} workload has no embedding head")
+    if int(getattr(args, "arc_eval_knn_vote", 0) or 0):
+        raise ValueError(f"--arc-eval-knn-vote: the kNN classification is wired for --workload arcface only; the "
+                         f"{workload} workload has no embedding head")
 
 
 def check_knn(args):
     k = int(getattr(args, "arc_eval_knn", 0) or 0)
     if not 0 <= k <= 8:
         raise ValueError(f"--arc-eval-knn covers 1 <= K <= 8 (0: off), got {k}")
+    kv = int(getattr(args, "arc_eval_knn_vote", 0) or 0)
+    if not 0 <= kv <= 256:
+        raise ValueError(f"--arc-eval-knn-vote covers 1 <= K <= 256 (0: off), got {kv}")
+    if kv and not float(getattr(args, "arc_knn_temperature", 0.07)) > 0:
+        raise ValueError(f"--arc-knn-temperature must be positive, got {args.arc_knn_temperature}")
 
 
 def _cuda_available() -> bool:

@@ -2254,6 +2254,69 @@ std::tuple<Tensor, Tensor, Tensor> knn_topk(const Tensor& qn, const Tensor& gn, 
   return {val, idx, hit};
 }
 
+int64_t knn_wide_splits(int64_t Nqp, int64_t Ngp) { return dcp::knn_wide_splits((int)Nqp, (int)Ngp); }
+
+// the same for 1 <= k <= 256 (knn_wide.hip) -> (val [Nq][k] fp32, idx [Nq][k] int32)
+std::tuple<Tensor, Tensor> knn_topk_wide(const Tensor& qn, const Tensor& gn, int64_t Nq, int64_t Ng, int64_t k,
+                                         int64_t splits, const optional<Tensor>& exclude) {
+  CHECK_ACT(qn);
+  CHECK_ACT(gn);
+  const int Nqp = qn.size(0), Ngp = gn.size(0), Dp = qn.size(1);
+  TORCH_CHECK(gn.size(1) == Dp && Nq >= 1 && Nq <= Nqp && Ng >= 1 && Ng <= Ngp, "knn_topk_wide shapes");
+  TORCH_CHECK(k >= 1 && k <= 256, "knn_topk_wide: 1 <= k <= 256, got ", k);
+  TORCH_CHECK(splits >= 1 && splits <= 64, "knn_topk_wide: 1 <= splits <= 64, got ", splits);
+  const int* ex = nullptr;
+  if (exclude.has_value()) {
+    TORCH_CHECK(exclude->is_cuda() && exclude->scalar_type() == at::kInt && exclude->is_contiguous() &&
+                    exclude->numel() == Nq,
+                "knn_topk_wide: exclude int32 [Nq]");
+    ex = exclude->data_ptr<int>();
+  }
+  const int64_t kcap = dcp::knn_wide_kcap((int)k);
+  auto iopt = qn.options().dtype(at::kInt);
+  auto pval = at::empty({splits * Nqp * kcap}, f32_like(qn));
+  auto pidx = at::empty({splits * Nqp * kcap}, iopt);
+  auto val = at::empty({Nq, k}, f32_like(qn));
+  auto idx = at::empty({Nq, k}, iopt);
+  TORCH_CHECK(dcp::launch_knn_topk_wide(bp(qn), bp(gn), (int)Nq, Nqp, (int)Ng, Ngp, Dp, (int)k, (int)splits, ex,
+                                        pval.data_ptr<float>(), pidx.data_ptr<int>(), val.data_ptr<float>(),
+                                        idx.data_ptr<int>(), cur_stream()),
+              "knn_topk_wide: unsupported shape (rows padded to 64, D padded to 128 / 256 / 512, k <= 256)");
+  return {val, idx};
+}
+
+// val fp32 / idx int32 [Nq][k], g_labels int64 [Ng], q_labels int64 [Nq] or none
+// -> (pred int64 [Nq], conf fp32 [Nq], agree fp32 [Nq] -- empty without q_labels)
+std::tuple<Tensor, Tensor, Tensor> knn_vote(const Tensor& val, const Tensor& idx, const Tensor& g_labels,
+                                            const optional<Tensor>& q_labels, double temperature, bool weighted) {
+  CHECK_DEV(val);
+  CHECK_DEV(idx);
+  CHECK_DEV(g_labels);
+  CHECK_CONTIG(val);
+  CHECK_CONTIG(idx);
+  CHECK_CONTIG(g_labels);
+  TORCH_CHECK(val.dim() == 2 && val.scalar_type() == at::kFloat && idx.scalar_type() == at::kInt &&
+                  idx.sizes() == val.sizes() && g_labels.scalar_type() == at::kLong && g_labels.dim() == 1,
+              "knn_vote: val fp32 / idx int32 [Nq][k], g_labels int64 [Ng]");
+  const int64_t Nq = val.size(0), k = val.size(1);
+  const int64_t* ql = nullptr;
+  if (q_labels.has_value()) {
+    TORCH_CHECK(q_labels->is_cuda() && q_labels->scalar_type() == at::kLong && q_labels->is_contiguous() &&
+                    q_labels->numel() == Nq,
+                "knn_vote: q_labels int64 [Nq]");
+    ql = q_labels->data_ptr<int64_t>();
+  }
+  auto pred = at::empty({Nq}, val.options().dtype(at::kLong));
+  auto conf = at::empty({Nq}, val.options());
+  auto agree = at::empty({ql ? Nq : 0}, val.options());
+  TORCH_CHECK(dcp::launch_knn_vote(val.data_ptr<float>(), idx.data_ptr<int>(), (int)Nq, (int)k, (int)g_labels.numel(),
+                                   g_labels.data_ptr<int64_t>(), ql, (float)temperature, weighted,
+                                   pred.data_ptr<int64_t>(), conf.data_ptr<float>(),
+                                   ql ? agree.data_ptr<float>() : nullptr, cur_stream()),
+              "knn_vote: 1 <= k <= 256, Nq >= 1, Ng >= 1, temperature > 0");
+  return {pred, conf, agree};
+}
+
 // ---------------------------------------------------------------------------
 // optimizers (multi-tensor). table: int64 [n,6] = (p, g, s1, s2, shadow, numel); chunks int32 [k,2]
 // ---------------------------------------------------------------------------
@@ -2720,6 +2783,11 @@ TORCH_LIBRARY(dcp, m) {
   m.def("knn_splits(int Nqp, int Ngp) -> int", &knn_splits);
   m.def("knn_topk(Tensor qn, Tensor gn, int Nq, int Ng, int k, int splits, Tensor? exclude, Tensor? q_labels, "
         "Tensor? g_labels) -> (Tensor, Tensor, Tensor)", &knn_topk);
+  m.def("knn_wide_splits(int Nqp, int Ngp) -> int", &knn_wide_splits);
+  m.def("knn_topk_wide(Tensor qn, Tensor gn, int Nq, int Ng, int k, int splits, Tensor? exclude) -> (Tensor, Tensor)",
+        &knn_topk_wide);
+  m.def("knn_vote(Tensor val, Tensor idx, Tensor g_labels, Tensor? q_labels, float temperature, bool weighted) "
+        "-> (Tensor, Tensor, Tensor)", &knn_vote);
   m.def("arcface_sub_l2norm_t(Tensor w, int Dp, float eps) -> (Tensor, Tensor, Tensor)", &arcface_sub_l2norm_t);
   m.def("arcface_sub_fwd(Tensor xn, Tensor wn, Tensor labels, int B, int C, int K, float s, float m, bool easy) -> "
         "(Tensor, Tensor, Tensor, Tensor, Tensor)", &arcface_sub_fwd);

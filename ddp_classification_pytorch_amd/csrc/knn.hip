@@ -371,4 +371,11 @@ bool launch_knn_topk(const bf16* qn, const bf16* gn, int Nq, int Nqp, int Ng, in
   return true;
 }
 
+// the merge alone, for the wide selection of knn_wide.hip (kmax = its KCAP)
+void launch_knn_merge(const float* pval, const int* pidx, int S, int kmax, int Nq, int Nqp, int k, float* val,
+                      int* idx, hipStream_t st) {
+  hipLaunchKernelGGL(knn_merge_kernel, dim3((Nq + 3) / 4), dim3(256), 0, st, pval, pidx, S, kmax, Nq, Nqp, k,
+                     (const int64_t*)nullptr, (const int64_t*)nullptr, val, idx, (int*)nullptr);
+}
+
 }  // namespace dcp

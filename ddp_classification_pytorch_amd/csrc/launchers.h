@@ -504,6 +504,21 @@ int knn_splits(int Nqp, int Ngp);
 bool launch_knn_topk(const bf16* qn, const bf16* gn, int Nq, int Nqp, int Ng, int Ngp, int Dp, int k, int S,
                      const int* exclude, const int64_t* q_labels, const int64_t* g_labels, float* pval, int* pidx,
                      float* val, int* idx, int* first_hit, hipStream_t st);
+void launch_knn_merge(const float* pval, const int* pidx, int S, int kmax, int Nq, int Nqp, int k, float* val,
+                      int* idx, hipStream_t st);
+// The same retrieval for 1 <= k <= 256 (knn_wide.hip: an LDS candidate pool per query row; same operands,
+// order and never-returned rules).  pval / pidx [S][Nqp][knn_wide_kcap(k)]; knn_wide_splits keeps
+// S Nqp < 32768 + Nqp, so the partials stay below (32768 + Nqp) KCAP 8 bytes.
+int knn_wide_kcap(int k);
+int knn_wide_splits(int Nqp, int Ngp);
+bool launch_knn_topk_wide(const bf16* qn, const bf16* gn, int Nq, int Nqp, int Ng, int Ngp, int Dp, int k, int S,
+                          const int* exclude, float* pval, int* pidx, float* val, int* idx, hipStream_t st);
+// kNN label vote over val / idx [Nq][k] (k <= 256; idx < 0 or >= Ng: no neighbour): weights
+// exp((val_j - val_0) / temperature) or 1, pred int64 [Nq] (-1: no neighbour), conf = vote(pred) / W,
+// agree = vote(q_label) / W (with q_labels only)
+bool launch_knn_vote(const float* val, const int* idx, int Nq, int k, int Ng, const int64_t* g_labels,
+                     const int64_t* q_labels, float temperature, bool weighted, int64_t* pred, float* conf,
+                     float* agree, hipStream_t st);
 // SyncBN peer-memory exchange (peer.hip): gather (mode 0, dst [world][n]) or rank-ordered sum
 // (mode 1, dst [n]) of n floats through the IPC-mapped mailboxes `boxes` ([world] base addresses);
 // a rank missing for timeout_ms sets *err and poisons dst with NaN (this and every later exchange)

@@ -34,6 +34,11 @@ Differences from the reference, all deliberate:
   and every sample retrieves its K nearest other validation samples (``Fn.cosine_topk``, the gallery
   all-gathered over the ranks); Recall@1 / @3 / @K go to ``val_knn`` records and ``VAL-KNN`` lines
   (under ``--model-ema`` also for the averaged weights, ``ema=True``).  ``best.pth`` stays with top-1.
+* ``--arc-eval-knn-vote K`` (ArcFace, K <= 256): the same embeddings (the set is embedded once for both
+  flags) classify every validation sample by the weighted vote of its K nearest other samples
+  (``Fn.cosine_topk`` / ``Fn.cosine_topk_wide`` + ``Fn.knn_vote``, weights exp(cos / T) with
+  ``--arc-knn-temperature``); ``val_knn_vote`` records and ``VAL-KNNVOTE`` lines carry top1 and the mean
+  share of the neighbours' weight that agrees with the sample's own label.
 """
 from __future__ import annotations
 
@@ -116,6 +121,43 @@ def knn_counts(feats, labels, k):
     return acc
 
 
+@torch.no_grad()
+def knn_vote_counts(feats, labels, k, temperature):
+    """Leave-one-out weighted kNN classification of this rank's rows against the gallery of ALL ranks'
+    rows, gathered as :func:`knn_counts` gathers it (rank 0's rows, then rank 1's, ...; every row excluded
+    at its own position).  -> fp64 [3] on the device: (#pred == label, sum of agree, n), this rank's
+    share (sum over the ranks with ``_allreduce``)."""
+    dev, n = feats.device, feats.shape[0]
+    labels = labels.reshape(-1).to(torch.int64)
+    gallery, glabels, off = feats, labels, 0
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        world, rank = dist.get_world_size(), dist.get_rank()
+        cdev = torch.device("cpu") if dist.get_backend() == "gloo" else dev  # gloo moves host tensors only
+        mine = torch.tensor([n, feats.shape[1]], dtype=torch.int64, device=cdev)
+        sizes = [torch.zeros_like(mine) for _ in range(world)]
+        dist.all_gather(sizes, mine)
+        counts = [int(t[0]) for t in sizes]
+        m, D = max(max(counts), 1), max(int(t[1]) for t in sizes)
+        fbuf = torch.zeros(m, D, dtype=torch.float32, device=cdev)
+        ybuf = torch.zeros(m, dtype=torch.int64, device=cdev)
+        fbuf[:n], ybuf[:n] = feats.float().to(cdev), labels.to(cdev)
+        fall = [torch.empty_like(fbuf) for _ in range(world)]
+        yall = [torch.empty_like(ybuf) for _ in range(world)]
+        dist.all_gather(fall, fbuf)
+        dist.all_gather(yall, ybuf)
+        gallery = torch.cat([f[:c] for f, c in zip(fall, counts)]).to(dev)
+        glabels = torch.cat([y[:c] for y, c in zip(yall, counts)]).to(dev)
+        off = sum(counts[:rank])
+        feats = fbuf[:n].to(dev)  # the same fp32 rows the gallery holds
+    acc = torch.zeros(3, dtype=torch.float64, device=dev)
+    if n:
+        own = torch.arange(off, off + n, dtype=torch.int32, device=dev)
+        pred, _, agree = Fn.knn_classify(feats, gallery, glabels, k, q_labels=labels, temperature=temperature,
+                                         exclude=own)
+        acc += torch.stack([(pred == labels).sum().double(), agree.double().sum(), agree.new_tensor(n).double()])
+    return acc
+
+
 class ClassificationLoop:
     """``forward_train(batch) -> (loss, rank)``; ``forward_eval(batch) -> (loss_rows, rank)``;
     optional ``post_backward()`` (e.g. CDR gradient masking) and ``epoch_hook(epoch)``."""
@@ -133,6 +175,11 @@ class ClassificationLoop:
         self.embed_eval, self.knn_k = embed_eval, int(getattr(args, "arc_eval_knn", 0) or 0)
         if self.knn_k and embed_eval is None:
             raise ValueError("--arc-eval-knn needs a workload that provides embeddings (arcface)")
+        # --arc-eval-knn-vote K: weighted kNN classification on the same embeddings
+        self.knn_vote_k = int(getattr(args, "arc_eval_knn_vote", 0) or 0)
+        self.knn_temperature = float(getattr(args, "arc_knn_temperature", 0.07))
+        if self.knn_vote_k and embed_eval is None:
+            raise ValueError("--arc-eval-knn-vote needs a workload that provides embeddings (arcface)")
         self.logger = logger or MetricsLogger(args.out_dir if rt.is_main else None)
         self.scheduler_before_epoch = scheduler_before_epoch  # CDR steps its scheduler before training (:365-366)
         self.train_modules = train_modules or list(models.values())
@@ -379,9 +426,8 @@ class ClassificationLoop:
         return {"loss": tot[0] / n, "top1": tot[1] / n, "top3": tot[2] / n, "count": tot[3]}
 
     @torch.no_grad()
-    def evaluate_knn(self):
-        """Retrieval Recall@1 / @3 / @K of the validation set against itself (each sample's own row
-        excluded), over the sampler's valid rows of every rank."""
+    def embed_val(self):
+        """(embeddings [n, D], labels [n]) of the sampler's valid validation rows of this rank."""
         for m in self.train_modules:
             m.eval()
         left = valid_count(getattr(self.val_data, "sampler", None), float("inf"))
@@ -395,7 +441,14 @@ class ClassificationLoop:
                 ys.append(batch[1][:k])
         if not fs:  # a rank without valid rows still takes part in the gathering
             fs, ys = [torch.zeros(0, 1, device=self.rt.device)], [torch.zeros(0, dtype=torch.int64, device=self.rt.device)]
-        tot = _allreduce(knn_counts(torch.cat(fs), torch.cat(ys), self.knn_k)).tolist()
+        return torch.cat(fs), torch.cat(ys)
+
+    @torch.no_grad()
+    def evaluate_knn(self, embedded=None):
+        """Retrieval Recall@1 / @3 / @K of the validation set against itself (each sample's own row
+        excluded), over the sampler's valid rows of every rank."""
+        feats, labels = embedded if embedded is not None else self.embed_val()
+        tot = _allreduce(knn_counts(feats, labels, self.knn_k)).tolist()
         n = max(tot[3], 1)
         out = {"k": self.knn_k, "recall1": tot[1] / n}
         if self.knn_k >= 3:
@@ -403,12 +456,27 @@ class ClassificationLoop:
         out.update(recallK=tot[0] / n, n=tot[3])
         return out
 
-    def _log_knn(self, epoch, tag, **extra):
-        kn = self.evaluate_knn()
-        self.logger.log("val_knn", epoch=epoch, **kn, **extra)
-        ks = [(1, "recall1")] + ([(3, "recall3")] if self.knn_k > 3 else []) + ([(self.knn_k, "recallK")] if self.knn_k > 1 else [])
-        self.logger.line(f"{tag} Epoch {epoch + 1}: " + " ".join(f"recall@{k} {100 * kn[key]:.3f}" for k, key in ks) +
-                         f" (n={int(kn['n'])})")
+    @torch.no_grad()
+    def evaluate_knn_vote(self, embedded=None):
+        """Leave-one-out weighted kNN classification of the validation set (``--arc-eval-knn-vote``)."""
+        feats, labels = embedded if embedded is not None else self.embed_val()
+        tot = _allreduce(knn_vote_counts(feats, labels, self.knn_vote_k, self.knn_temperature)).tolist()
+        n = max(tot[2], 1)
+        return {"k": self.knn_vote_k, "T": self.knn_temperature, "top1": tot[0] / n, "agree": tot[1] / n, "n": tot[2]}
+
+    def _log_knn(self, epoch, suffix="", **extra):
+        embedded = self.embed_val()  # once for both evaluations
+        if self.knn_k:
+            kn = self.evaluate_knn(embedded)
+            self.logger.log("val_knn", epoch=epoch, **kn, **extra)
+            ks = [(1, "recall1")] + ([(3, "recall3")] if self.knn_k > 3 else []) + ([(self.knn_k, "recallK")] if self.knn_k > 1 else [])
+            self.logger.line(f"VAL-KNN{suffix} Epoch {epoch + 1}: " +
+                             " ".join(f"recall@{k} {100 * kn[key]:.3f}" for k, key in ks) + f" (n={int(kn['n'])})")
+        if self.knn_vote_k:
+            kv = self.evaluate_knn_vote(embedded)
+            self.logger.log("val_knn_vote", epoch=epoch, **kv, **extra)
+            self.logger.line(f"VAL-KNNVOTE{suffix} Epoch {epoch + 1}: k {kv['k']} T {kv['T']:g} top1 {100 * kv['top1']:.3f} "
+                             f"agree {100 * kv['agree']:.3f} (n={int(kv['n'])})")
 
     def run(self):
         a = self.args
@@ -425,8 +493,8 @@ class ClassificationLoop:
                 self.logger.line(f"VAL Epoch {epoch + 1}: loss {va['loss']:.4f} top1 {100 * va['top1']:.3f} "
                                  f"top3 {100 * va['top3']:.3f} (n={int(va['count'])}) | train loss {tr['loss']:.4f} "
                                  f"top1 {100 * tr['top1']:.3f} ({tr['time']:.1f}s)")
-                if self.knn_k:
-                    self._log_knn(epoch, "VAL-KNN")
+                if self.knn_k or self.knn_vote_k:
+                    self._log_knn(epoch)
                 if self.ema is not None:
                     with self.ema.applied():  # the live model computes on the averages; every bit comes back
                         ve = self.evaluate()
@@ -434,9 +502,9 @@ class ClassificationLoop:
                     self.logger.line(f"VAL-EMA Epoch {epoch + 1}: loss {ve['loss']:.4f} top1 {100 * ve['top1']:.3f} "
                                      f"top3 {100 * ve['top3']:.3f} (n={int(ve['count'])}, "
                                      f"{self.ema.num_updates} updates)")
-                    if self.knn_k:
+                    if self.knn_k or self.knn_vote_k:
                         with self.ema.applied():
-                            self._log_knn(epoch, "VAL-KNN-EMA", ema=True)
+                            self._log_knn(epoch, "-EMA", ema=True)
             if self.scheduler is not None and not self.scheduler_before_epoch:
                 self.scheduler.step()
             if (epoch + 1) % a.save_every == 0 or epoch + 1 == a.epochs:

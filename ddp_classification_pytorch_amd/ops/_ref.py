@@ -981,6 +981,35 @@ def cosine_topk(q, g, k, normalize, exclude, q_labels, g_labels):
     return val, idx, hit
 
 
+def knn_vote(val, idx, g_labels, q_labels, temperature, weighted):
+    """Reference math of knn_vote_kernel (csrc/knn_wide.hip): fp32 weights, votes and W summed in
+    ascending j.  -> (pred int64 [Nq], conf [Nq], agree [Nq] or None)."""
+    val = _f(val)
+    Nq, k = val.shape
+    valid = idx >= 0
+    lab = g_labels.long()[idx.clamp(min=0).long()]
+    w = torch.exp((val - val[:, :1]) / temperature) if weighted else torch.ones_like(val)
+    w = torch.where(valid, w, torch.zeros_like(w))
+    yq = None if q_labels is None else q_labels.long().view(-1, 1)
+    votes = torch.zeros_like(val)  # votes[r, m] = vote(label of neighbour m)
+    W, vq = val.new_zeros(Nq, 1), val.new_zeros(Nq, 1)
+    for j in range(k):
+        wj, lj = w[:, j:j + 1], lab[:, j:j + 1]
+        votes = votes + wj * (lab == lj)
+        W = W + wj
+        if yq is not None:
+            vq = vq + wj * (lj == yq)
+    any_ = valid.any(1)
+    best = torch.where(valid, votes, torch.full_like(votes, -1.0)).amax(1, keepdim=True)
+    big = torch.iinfo(torch.int64).max
+    pred = torch.where(valid & (votes == best), lab, torch.full_like(lab, big)).amin(1)
+    pred = torch.where(any_, pred, torch.full_like(pred, -1))
+    Ws = torch.where(any_, W.squeeze(1), torch.ones_like(W.squeeze(1)))
+    conf = torch.where(any_, best.squeeze(1) / Ws, torch.zeros_like(Ws))
+    agree = None if yq is None else torch.where(any_, vq.squeeze(1) / Ws, torch.zeros_like(Ws))
+    return pred, conf, agree
+
+
 def transpose2d(x):
     return x.t().contiguous()
 

@@ -2005,6 +2005,84 @@ def cosine_topk(q, g, k, normalize=True, exclude=None, q_labels=None, g_labels=N
     return (val, idx) if ql is None else (val, idx, hit)
 
 
+KNN_WIDE_MAX_K = 256
+
+
+@torch.no_grad()
+def cosine_topk_wide(q, g, k, normalize=True, exclude=None, splits=None):
+    """:func:`cosine_topk` for 1 <= k <= 256 -> (val fp32 [Nq, k], idx int32 [Nq, k]): the same order
+    (score descending, then gallery index ascending), the same never-returned rules (``exclude``, NaN
+    scores, padding) and the same (-inf, -1) tail, D <= 512.
+
+    On the GPU the candidate-pool kernel of csrc/knn_wide.hip on the operands of :func:`knn_operand`:
+    nothing [Nq, Ng] is written, the split partials stay below (32768 + Nq) * 256 * 8 bytes, and the
+    bits depend neither on ``splits`` (1..64, default a heuristic) nor on the run.  On the CPU the
+    reference math of ``_ref.cosine_topk``."""
+    k = int(k)
+    for x, name in ((q, "q"), (g, "g")):
+        if x.dim() != 2 or x.dtype not in (torch.float32, torch.bfloat16) or x.shape[0] < 1:
+            raise ValueError(f"cosine_topk_wide takes fp32 or bf16 rows [N, D], got {name} {x.dtype} {tuple(x.shape)}")
+        if not 1 <= x.shape[1] <= KNN_MAX_D:
+            raise ValueError(f"cosine_topk_wide covers 1 <= D <= {KNN_MAX_D}, got D = {x.shape[1]}")
+    if q.shape[1] != g.shape[1] or q.device != g.device:
+        raise ValueError(f"cosine_topk_wide: q {tuple(q.shape)} on {q.device} and g {tuple(g.shape)} on {g.device}")
+    if not 1 <= k <= KNN_WIDE_MAX_K:
+        raise ValueError(f"cosine_topk_wide covers 1 <= k <= {KNN_WIDE_MAX_K}, got k = {k}")
+    Nq, Ng = q.shape[0], g.shape[0]
+    if exclude is not None and exclude.numel() != Nq:
+        raise ValueError(f"cosine_topk_wide: exclude holds {exclude.numel()} entries for {Nq} queries")
+    if not q.is_cuda:
+        return _ref.cosine_topk(q, g, k, bool(normalize), exclude, None, None)[:2]
+    ops = K(q)
+    qn = knn_operand(q, normalize)
+    gn = qn if g is q else knn_operand(g, normalize)
+    S = int(splits) if splits is not None else ops.knn_wide_splits(qn.shape[0], gn.shape[0])
+    if not 1 <= S <= 64:
+        raise ValueError(f"cosine_topk_wide: 1 <= splits <= 64, got {S}")
+    ex = None if exclude is None else exclude.to(device=q.device, dtype=torch.int32).contiguous()
+    return ops.knn_topk_wide(qn, gn, Nq, Ng, k, S, ex)
+
+
+@torch.no_grad()
+def knn_vote(val, idx, g_labels, q_labels=None, temperature=0.07, weighted=True):
+    """The kNN label vote over the neighbours ``val`` / ``idx`` [Nq, k] (k <= 256) of either top-k op
+    -> (pred int64 [Nq], conf fp32 [Nq], agree fp32 [Nq] or None without ``q_labels``).
+
+    Neighbour j is valid when ``idx_j >= 0`` and weighs ``exp((val_j - val_0) / temperature)`` in fp32
+    (``weighted=False``: 1, the majority vote).  vote(c) is the sum of the weights of the valid
+    neighbours of label c and W the sum of all of them, both in ascending j.  ``pred`` is the class of
+    the largest vote, the smallest class id among equal votes, -1 without a valid neighbour;
+    ``conf = vote(pred) / W`` and ``agree = vote(q_label) / W`` (0 without a valid neighbour): a sample
+    whose neighbours outvote its own label has a small ``agree``.  On the GPU knn_vote_kernel
+    (csrc/knn_wide.hip, one wave per row, no [Nq, C] vote matrix), on the CPU ``_ref.knn_vote``."""
+    if val.dim() != 2 or idx.shape != val.shape or not 1 <= val.shape[1] <= KNN_WIDE_MAX_K or val.shape[0] < 1:
+        raise ValueError(f"knn_vote takes val and idx [Nq, k] with 1 <= k <= {KNN_WIDE_MAX_K}, got "
+                         f"{tuple(val.shape)} and {tuple(idx.shape)}")
+    if not float(temperature) > 0:
+        raise ValueError(f"knn_vote: temperature > 0, got {temperature}")
+    if q_labels is not None and q_labels.numel() != val.shape[0]:
+        raise ValueError("knn_vote: one label per query row")
+    if g_labels.dim() != 1 or g_labels.numel() < 1:
+        raise ValueError("knn_vote: g_labels [Ng]")
+    if not val.is_cuda:
+        return _ref.knn_vote(val, idx, g_labels, q_labels, float(temperature), bool(weighted))
+    dev = val.device
+    ql = None if q_labels is None else q_labels.to(device=dev, dtype=torch.int64).contiguous()
+    pred, conf, agree = K(val).knn_vote(val.float().contiguous(), idx.to(torch.int32).contiguous(),
+                                        g_labels.to(device=dev, dtype=torch.int64).contiguous(), ql,
+                                        float(temperature), bool(weighted))
+    return pred, conf, (agree if ql is not None else None)
+
+
+@torch.no_grad()
+def knn_classify(q, g, g_labels, k, q_labels=None, temperature=0.07, weighted=True, normalize=True, exclude=None):
+    """Top-k retrieval and the label vote in sequence: :func:`cosine_topk` for k <= 8,
+    :func:`cosine_topk_wide` above, then :func:`knn_vote` -> (pred, conf, agree or None)."""
+    top = cosine_topk if int(k) <= KNN_MAX_K else cosine_topk_wide
+    val, idx = top(q, g, k, normalize=normalize, exclude=exclude)
+    return knn_vote(val, idx, g_labels, q_labels, temperature, weighted)
+
+
 # ----------------------------------------------------------------------------- misc
 def s2d_block(s2d) -> int:
     """The space-to-depth block of an input-layout ``s2d`` value: False / 0 none, True / 2 the

@@ -2,7 +2,11 @@
 matrix [Nq, Ng] through the MFMA linear kernel (l2norm_rows + linear_fwd, as Fn.arcface_rows builds it)
 followed by torch.topk.
 
-    python tools/knn_bench.py [--shapes 10000x256,50000x256,50000x512] [--ks 1,8] [--rounds 5] [--out FILE]
+    python tools/knn_bench.py [--shapes 10000x256,50000x256,50000x512] [--ks 1,8] [--rounds 5] [--wide] [--out FILE]
+
+A k above 8 (or any k under ``--wide``) adds the wide route Fn.cosine_topk_wide (csrc/knn_wide.hip) and
+Fn.knn_classify (the wide top-k followed by the weighted label vote over 100 random classes); the
+k <= 8 kernel is timed only where it applies.
 
 A shape NxD is Nq = Ng = N rows of width D, the validation set against itself (no exclusion: the unfused
 route has none).  Timing: HIP events around blocks of calls after a warm-up, the two arms alternating
@@ -49,6 +53,7 @@ def main(argv=None):
     ap.add_argument("--shapes", default="10000x256,50000x256,50000x512")
     ap.add_argument("--ks", default="1,8")
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--wide", action="store_true", help="time Fn.cosine_topk_wide at k <= 8 too")
     ap.add_argument("--out", default=None)
     a = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -57,10 +62,12 @@ def main(argv=None):
     dev = torch.device("cuda", 0)
     lines = [f"# knn_bench: Nq = Ng = N, {a.rounds} alternating blocks per arm, median [min .. max] ms per call",
              f"# device: {torch.cuda.get_device_name(0)}",
-             "# fused: Fn.cosine_topk; unfused: l2norm_rows + linear_fwd (bf16 [Nq, Ng]) + torch.topk"]
+             "# fused: Fn.cosine_topk; unfused: l2norm_rows + linear_fwd (bf16 [Nq, Ng]) + torch.topk",
+             "# wide: Fn.cosine_topk_wide; classify: Fn.knn_classify (top-k + weighted vote)"]
     for shape in a.shapes.split(","):
         N, D = (int(v) for v in shape.split("x"))
         x = torch.randn(N, D, device=dev, generator=torch.Generator(dev).manual_seed(N + D))
+        y = torch.randint(0, 100, (N,), device=dev)
         Dp, Np = Fn.arcface_fused_dp(D), Fn.round_up(N, 64)
         flop = 2.0 * Np * Np * Dp
         steps = max(2, min(50, int(2e9 / (N * N))))  # ~ a quarter second and more of work per block
@@ -81,8 +88,13 @@ def main(argv=None):
                          for r in range(0, N, chunk)]
                 return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
 
-            arms = {"fused": fused, "unfused": unfused}
-            fv, uv = fused()[0], unfused()[0].float()
+            arms = {"fused": fused} if k <= Fn.KNN_MAX_K else {}
+            if k > Fn.KNN_MAX_K or a.wide:
+                arms["wide"] = lambda: Fn.cosine_topk_wide(x, x, k)  # noqa: B023 - called inside this iteration
+                arms["classify"] = lambda: Fn.knn_classify(x, x, y, k)  # noqa: B023
+            arms["unfused"] = unfused
+            first = next(iter(arms))
+            fv, uv = arms[first]()[0], unfused()[0].float()
             worst = (fv[:, 0] - uv[:, 0]).abs().max().item()  # self-matches: cosine 1 on both routes
             mem = {n: _peak_extra(f) for n, f in arms.items()}
             for f in arms.values():
@@ -93,13 +105,15 @@ def main(argv=None):
                     t[n].append(_time_block(f, steps))
             med = {n: statistics.median(v) for n, v in t.items()}
             lines.append(f"N {N:6d} D {D:3d} k {k}: MFMA work {flop / 1e12:.3f} TFLOP, {steps} calls per block, "
-                         f"|fused - unfused| first value {worst:.1e}")
+                         f"|{first} - unfused| first value {worst:.1e}")
             for n in arms:
-                rate = f"   {flop / med[n] / 1e9:7.1f} TFLOP/s of MFMA work" if n == "fused" else ""
+                rate = f"   {flop / med[n] / 1e9:7.1f} TFLOP/s of MFMA work" if n != "unfused" else ""
                 lines.append(f"    {n:8s} {med[n]:9.3f} ms  [{min(t[n]):.3f} .. {max(t[n]):.3f}]   "
                              f"extra memory {mem[n] / 2**20:8.1f} MB{rate}")
-            lines.append(f"    unfused / fused time {med['unfused'] / med['fused']:.2f}x, memory "
-                         f"{mem['unfused'] / max(mem['fused'], 1):.1f}x")
+            for n in arms:
+                if n != "unfused":
+                    lines.append(f"    unfused / {n} time {med['unfused'] / med[n]:.2f}x, memory "
+                                 f"{mem['unfused'] / max(mem[n], 1):.1f}x")
         del x
         torch.cuda.empty_cache()
     text = "\n".join(lines)
