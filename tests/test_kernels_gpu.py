@@ -662,12 +662,20 @@ def test_s2d_stem_gpu_matches_plain_stem():
     assert relerr(g1, g0) < 1e-2
 
 
-@pytest.mark.parametrize("size,batch", [(64, 4), (96, 3), (224, 2), (112, 3)])  # 112: W = 56, half tiles
+# 112: W = 56, half tiles; (64, 20) and (32, 40): W = 32 and W = 16 over 640 rows, several rows per workgroup
+FUSED_STEM_CASES = [(64, 4), (96, 3), (224, 2), (112, 3), (64, 20), (32, 40)]
+
+
+@pytest.mark.parametrize("size,batch", FUSED_STEM_CASES)
 def test_fused_stem_matches_unfused(size, batch):
     """The one-op stem (stem conv + BN + ReLU + max pool, one-pass fused backward in stem.hip)
     against the unfused chain (stem conv, BN+ReLU+pool, two-pass BN/pool backward, implicit-GEMM
     weight gradient) on a ResNet-18: loss, stem / BN1 gradients and a deep layer's gradient."""
     import copy
+    # the fused backward runs min(rows, CUs) workgroups over ceil(rows / workgroups) rows each (rows = batch x
+    # size / 2): on this device at least one case must run its steady-state loop, not one row per workgroup
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert any(-(-(b * s // 2) // min(b * s // 2, cus)) > 1 for s, b in FUSED_STEM_CASES), cus
     from ddp_classification_pytorch_amd.models import build_model, input_layout
     from ddp_classification_pytorch_amd.models import resnet as R
     from ddp_classification_pytorch_amd.ops import functional as Fn
