@@ -15,6 +15,11 @@ label-free retrieval evaluation (engine/loop.py ``evaluate_knn``): Recall@1 / @3
 validation embedding against the other validation embeddings.  ``--arc-eval-knn-vote K`` (K <= 256,
 ``--arc-knn-temperature``) classifies every validation embedding by the weighted vote of its K nearest
 other validation embeddings (``evaluate_knn_vote``).
+
+``--arc-sample-rate R`` < 1 trains with Partial FC (``Fn.arcface_partial_loss``): each step scores a
+row against the batch's labels and a share R of the other classes, drawn on the device; each rank
+samples against its own labels and the dense weight gradient is all-reduced as ever.  Evaluation
+keeps the full head.
 """
 from __future__ import annotations
 
@@ -51,7 +56,7 @@ def build_arcface(args):
         load_pretrained(backbone, args.pretrained)
     embed = MLPHead(backbone.feat_dim, args.hidden, args.embed_dim, log_softmax=True)
     arc = ArcMarginProduct(args.embed_dim, args.num_classes, s=args.arc_s, m=args.arc_m, easy_margin=args.easy_margin,
-                           sub_centers=args.arc_sub_centers)
+                           sub_centers=args.arc_sub_centers, sample_rate=getattr(args, "arc_sample_rate", 1.0))
     return ArcFaceModel(backbone, embed, arc)
 
 

@@ -191,6 +191,9 @@ def build_parser() -> argparse.ArgumentParser:
     a("--arc-sub-centers", type=int, default=1,
       help="Sub-center ArcFace: K centres per class, a sample scored against the nearest one (1: plain ArcFace; "
            "the fused head covers 2..4 at an embedding width <= 256)")
+    a("--arc-sample-rate", type=float, default=1.0,
+      help="Partial FC: each training step scores a row against the batch's labels and this share of the other "
+           "classes, drawn on the device (1.0: the full head; not with --arc-sub-centers > 1)")
     # CDR (unused reference flags accepted for CLI compatibility)
     a("--noise_rate", "--noise-rate", dest="noise_rate", type=float, default=0.2)
     a("--num_gradual", type=int, default=10)
@@ -292,9 +295,19 @@ def refuse_knn(args, workload: str):
     if int(getattr(args, "arc_eval_knn_vote", 0) or 0):
         raise ValueError(f"--arc-eval-knn-vote: the kNN classification is wired for --workload arcface only; the "
                          f"{workload} workload has no embedding head")
+    if float(getattr(args, "arc_sample_rate", 1.0)) != 1.0:
+        raise ValueError(f"--arc-sample-rate: Partial FC is wired for --workload arcface only; the {workload} "
+                         f"workload has no ArcFace head")
 
 
 def check_knn(args):
+    """The ArcFace workload's flag check (retrieval evaluation, Partial FC)."""
+    r = float(getattr(args, "arc_sample_rate", 1.0))
+    if not 0.0 < r <= 1.0:
+        raise ValueError(f"--arc-sample-rate covers 0 < R <= 1 (1: the full head), got {r}")
+    if r < 1.0 and int(getattr(args, "arc_sub_centers", 1)) > 1:
+        raise ValueError("--arc-sample-rate < 1 covers --arc-sub-centers 1 only (the sampled head has no sub-centre "
+                         "kernel)")
     k = int(getattr(args, "arc_eval_knn", 0) or 0)
     if not 0 <= k <= 8:
         raise ValueError(f"--arc-eval-knn covers 1 <= K <= 8 (0: off), got {k}")

@@ -2196,6 +2196,67 @@ Tensor arcface_sub_dw(const Tensor& xn, const Tensor& xnT, const Tensor& wn, con
   return dw;
 }
 
+// Partial FC (arcface_pfc.hip).  labels int64 [B] -> (idx int32 [round_up(Cs, 64)]: the Cs sampled classes
+// ascending, -1 tail; slot int32 [C]; lab int64 [B]).  `step` int64[1] is the device call counter, bumped
+// here after the launches (graph-capturable), as dropout_fwd bumps its offset
+std::tuple<Tensor, Tensor, Tensor> pfc_sample(const Tensor& labels, int64_t C, int64_t Cs, int64_t seed,
+                                              const Tensor& step) {
+  CHECK_DEV(labels);
+  CHECK_CONTIG(labels);
+  CHECK_DEV(step);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.dim() == 1 && labels.numel() >= 1, "pfc_sample: labels int64 [B]");
+  TORCH_CHECK(step.scalar_type() == at::kLong && step.numel() == 1, "pfc_sample: step int64[1]");
+  const int64_t B = labels.numel();
+  TORCH_CHECK(C >= 1 && C < (int64_t(1) << 31) - 4096 && B < (int64_t(1) << 31) - 4096, "pfc_sample: B, C < 2^31");
+  TORCH_CHECK(Cs <= C && Cs >= std::min(B, C), "pfc_sample: min(B, C) <= Cs <= C, got Cs = ", Cs);
+  const auto i32 = labels.options().dtype(at::kInt);
+  auto idx = at::empty({(Cs + 63) / 64 * 64}, i32);
+  auto slot = at::empty({C}, i32);
+  auto lab = at::empty({B}, labels.options());
+  auto ws = at::empty({(int64_t)dcp::pfc_workspace_words((int)C)}, i32);
+  TORCH_CHECK(dcp::launch_pfc_sample(labels.data_ptr<int64_t>(), (int)B, (int)C, (int)Cs, (uint64_t)seed,
+                                     step.data_ptr<int64_t>(), ws.data_ptr<int>(), idx.data_ptr<int>(),
+                                     slot.data_ptr<int>(), lab.data_ptr<int64_t>(), cur_stream()),
+              "pfc_sample: unsupported shape");
+  step.add_(1);
+  return {idx, slot, lab};
+}
+
+// rows w[idx[r]] of w [C][D] fp32 -> (y [Rp][Dp] bf16 normalised rows, yT [Dp][Rp], inverse norms [Rp]),
+// Rp = idx.numel(); a zero row where idx is -1
+std::tuple<Tensor, Tensor, Tensor> arcface_gather_l2norm_t(const Tensor& w, const Tensor& idx, int64_t Dp, double eps) {
+  CHECK_DEV(w);
+  CHECK_CONTIG(w);
+  CHECK_F32(w);
+  CHECK_DEV(idx);
+  CHECK_CONTIG(idx);
+  TORCH_CHECK(w.dim() == 2 && idx.scalar_type() == at::kInt && idx.dim() == 1, "arcface_gather_l2norm_t: w [C][D], idx int32");
+  const int64_t Rp = idx.numel();
+  auto y = at::empty({Rp, Dp}, w.options().dtype(at::kBFloat16));
+  auto yT = at::empty({Dp, Rp}, w.options().dtype(at::kBFloat16));
+  auto inv = at::empty({Rp}, w.options());
+  TORCH_CHECK(dcp::launch_arcface_gather_l2norm_t(w.data_ptr<float>(), idx.data_ptr<int>(), w.size(0), w.size(1), (int)Rp,
+                                                  (int)Dp, bpm(y), bpm(yT), inv.data_ptr<float>(), (float)eps,
+                                                  cur_stream()),
+              "arcface_gather_l2norm_t: idx.numel() % 64, D <= Dp in {128, 256, 512}");
+  return {y, yT, inv};
+}
+
+// dense [C][D] from the compact rows src [Cs][D]: row c = src[slot[c]], or zeros where slot[c] is -1
+Tensor arcface_scatter_rows(const Tensor& src, const Tensor& slot) {
+  CHECK_DEV(src);
+  CHECK_CONTIG(src);
+  CHECK_F32(src);
+  CHECK_DEV(slot);
+  CHECK_CONTIG(slot);
+  TORCH_CHECK(src.dim() == 2 && slot.scalar_type() == at::kInt && slot.dim() == 1, "arcface_scatter_rows: src [Cs][D], slot int32 [C]");
+  auto dst = at::empty({slot.numel(), src.size(1)}, src.options());
+  TORCH_CHECK(dcp::launch_arcface_scatter_rows(src.data_ptr<float>(), slot.data_ptr<int>(), (int)slot.numel(),
+                                               (int)src.size(0), (int)src.size(1), dst.data_ptr<float>(), cur_stream()),
+              "arcface_scatter_rows: empty operand");
+  return dst;
+}
+
 // Fused top-k retrieval (knn.hip).  x [R][D] fp32 / bf16 -> bf16 operand rows [Rp][Dp] (zero padding),
 // L2-normalised or just converted
 Tensor knn_prep(const Tensor& x, int64_t Rp, int64_t Dp, bool normalize, double eps) {
@@ -2779,6 +2840,10 @@ TORCH_LIBRARY(dcp, m) {
         "float scale, Tensor inv_x, int B, int C, int D, float s, bool out_bf16) -> Tensor", &arcface_fused_dx);
   m.def("arcface_fused_dw(Tensor xn, Tensor xnT, Tensor wn, Tensor labels, Tensor lse, Tensor lab, Tensor grad_out, "
         "float scale, Tensor inv_w, int B, int C, int D, float s) -> Tensor", &arcface_fused_dw);
+  m.def("pfc_sample(Tensor labels, int C, int Cs, int seed, Tensor(a!) step) -> (Tensor, Tensor, Tensor)", &pfc_sample);
+  m.def("arcface_gather_l2norm_t(Tensor w, Tensor idx, int Dp, float eps) -> (Tensor, Tensor, Tensor)",
+        &arcface_gather_l2norm_t);
+  m.def("arcface_scatter_rows(Tensor src, Tensor slot) -> Tensor", &arcface_scatter_rows);
   m.def("knn_prep(Tensor x, int Rp, int Dp, bool normalize, float eps) -> Tensor", &knn_prep);
   m.def("knn_splits(int Nqp, int Ngp) -> int", &knn_splits);
   m.def("knn_topk(Tensor qn, Tensor gn, int Nq, int Ng, int k, int splits, Tensor? exclude, Tensor? q_labels, "

@@ -218,5 +218,21 @@ __device__ __forceinline__ uint32_t xcd_remap(uint32_t orig, uint32_t nwg) {
   return base + idx;
 }
 
+// Philox-4x32-10 (Salmon et al., SC 2011): counter c[4] -> 4 random words in place, key (k0, k1).
+// Shared by the dropout mask (misc.hip) and the Partial FC class sampler (arcface_pfc.hip).
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
+    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
+    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = lo1;
+    c[2] = n2;
+    c[3] = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
 
 }  // namespace dcp

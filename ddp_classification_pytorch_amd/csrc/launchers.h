@@ -491,6 +491,19 @@ bool launch_arcface_sub_dw(const bf16* xn, const bf16* xnT, const bf16* wn, cons
                            int C, int K, int Dp, int D, float s, const float* lab, const int* sub, const float* lse,
                            const float* gout, float scale, const float* inv_w, float* part, float* info, float* dw,
                            hipStream_t st);
+// Partial FC (arcface_pfc.hip): the class subset of a step, its compact operands, the dense gradient.
+// launch_pfc_sample: labels [B] -> idx [round_up(Cs, 64)] (the Cs sampled classes ascending, -1 tail),
+// slot [C] (position in idx or -1), lab [B] (slot of the label, -1 for an invalid one); min(B, C) <= Cs <= C;
+// *step_ptr is the device call counter (the caller bumps it), ws holds pfc_workspace_words(C) int32.
+// launch_arcface_gather_l2norm_t: launch_arcface_l2norm_t over the rows w[idx[r]] of w [C][D] (idx [Rp],
+// a zero row where idx is -1).  launch_arcface_scatter_rows: dst [C][D] row c = src [Cs][D] row slot[c],
+// or zeros.  false = unsupported shape.
+size_t pfc_workspace_words(int C);
+bool launch_pfc_sample(const int64_t* labels, int B, int C, int Cs, uint64_t seed, const int64_t* step_ptr, int* ws,
+                       int* idx, int* slot, int64_t* lab, hipStream_t st);
+bool launch_arcface_gather_l2norm_t(const float* w, const int* idx, int C, int D, int Rp, int Dp, bf16* y, bf16* yT,
+                                    float* inv, float eps, hipStream_t st);
+bool launch_arcface_scatter_rows(const float* src, const int* slot, int C, int Cs, int D, float* dst, hipStream_t st);
 // Fused top-k retrieval (knn.hip): no [Nq, Ng] tensor.  qn [Nqp][Dp] / gn [Ngp][Dp] bf16 operands from
 // launch_knn_prep (zero padding rows), Nqp % 64 == Ngp % 64 == 0, Dp in {128, 256, 512}, 1 <= k <= 8,
 // 1 <= S <= 64 gallery splits (knn_splits: the heuristic); false = unsupported.  Order: score descending,

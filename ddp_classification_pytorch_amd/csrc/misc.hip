@@ -676,23 +676,8 @@ void launch_nested_eval(const float* feat, const float* W, const int64_t* labels
 // counter (i / 4, 0, offset) under key `seed` is >= p.  The backward regenerates the same mask
 // from (seed, offset) -- nothing is stored.  The call offset lives in a device counter the
 // launcher bumps after the kernel (so a HIP-graph replay draws a fresh mask every replay); the
-// kernel copies the value it used to `used` for the backward.
+// kernel copies the value it used to `used` for the backward.  (philox4x32_10: common.cuh)
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t lo0 = 0xD2511F53u * c[0], hi0 = __umulhi(0xD2511F53u, c[0]);
-    const uint32_t lo1 = 0xCD9E8D57u * c[2], hi1 = __umulhi(0xCD9E8D57u, c[2]);
-    const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
-    c[0] = n0;
-    c[1] = lo1;
-    c[2] = n2;
-    c[3] = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-}
-
 template <typename T>
 __device__ __forceinline__ float ld_f(const T* p, size_t i) {
   if constexpr (sizeof(T) == 2) return bf2f(((const bf16*)p)[i]);

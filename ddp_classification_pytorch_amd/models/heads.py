@@ -45,16 +45,30 @@ class ArcMarginProduct(nn.Module):
     ``sub_centers`` = K > 1 is Sub-center ArcFace (Deng et al., ECCV 2020): weight [out, K, in]
     (xavier init over the [out * K, in] rows), a sample scored against the nearest of a class's K
     centres.  ``forward`` then keeps the winning centre of each row's label class in the
-    non-persistent buffer ``last_sub_idx`` (int32 [B])."""
+    non-persistent buffer ``last_sub_idx`` (int32 [B]).
 
-    def __init__(self, in_features=256, out_features=2173, s=30.0, m=0.50, easy_margin=True, sub_centers=1):
+    ``sample_rate`` < 1 is Partial FC (An et al., CVPR 2022): in training mode ``forward`` scores a
+    row against the batch's labels and a random share of the other classes
+    (:func:`Fn.arcface_partial_loss`) and keeps the sampled classes in the non-persistent buffer
+    ``last_sample_idx`` (int32 [Cs]); evaluation runs the full head.  Not with sub-centres."""
+
+    def __init__(self, in_features=256, out_features=2173, s=30.0, m=0.50, easy_margin=True, sub_centers=1,
+                 sample_rate=1.0):
         super().__init__()
+        self.sample_rate = float(sample_rate)
+        if not 0.0 < self.sample_rate <= 1.0:
+            raise ValueError(f"ArcMarginProduct covers 0 < sample_rate <= 1, got {sample_rate}")
+        if self.sample_rate < 1.0 and int(sub_centers) > 1:
+            raise ValueError("Partial FC (sample_rate < 1) covers sub_centers = 1 only: the sampled head has no "
+                             f"sub-centre kernel, got sub_centers = {sub_centers}")
         self.in_features, self.out_features = in_features, out_features
         self.s, self.m, self.easy_margin = s, m, easy_margin
         self.sub_centers = int(sub_centers)
         if self.sub_centers == 1:
             self.weight = nn.Parameter(torch.empty(out_features, in_features))
             nn.init.xavier_uniform_(self.weight)
+            if self.sample_rate < 1.0:
+                self.register_buffer("last_sample_idx", torch.zeros(0, dtype=torch.int32), persistent=False)
         else:
             Fn.arcface_sub_check(self.sub_centers, in_features)
             w = torch.empty(out_features * self.sub_centers, in_features)
@@ -66,6 +80,13 @@ class ArcMarginProduct(nn.Module):
 
     def forward(self, x, label, return_logits=False):
         """-> (mean CE loss over margin logits, label rank, margin logits or empty)."""
+        if self.sample_rate < 1.0 and self.training:
+            if return_logits:
+                raise ValueError("Partial FC (sample_rate < 1) writes no logits in training mode: return_logits "
+                                 "needs the full head (eval mode, or sample_rate = 1)")
+            loss, rank, self.last_sample_idx = Fn.arcface_partial_loss(x, self.weight, label, self.s, self.m,
+                                                                       self.easy_margin, self.sample_rate)
+            return loss, rank, torch.empty(0, device=x.device)
         if self.sub_centers == 1:
             return Fn.arcface_loss(x, self.weight, label, self.s, self.m, self.easy_margin, return_logits)
         loss, rank, logits, self.last_sub_idx = Fn.arcface_loss(x, self.weight, label, self.s, self.m,

@@ -1031,6 +1031,57 @@ def dropout_bwd(dy, p, seed, used):
     return (_f(dy) * _drop_mask(dy.shape, p, seed, int(used.item()), dy.device) / (1.0 - p)).to(dy.dtype)
 
 
+# ----------------------------------------------------------------------------- Partial FC sampler
+_M32 = 0xFFFFFFFF
+
+
+def _mul32(m, x):
+    """(high, low) 32-bit words of the product m * x (m a 32-bit constant, x int64 values < 2^32),
+    in int64 arithmetic that never passes 2^63: x is split into 16-bit halves."""
+    lo, hi = m * (x & 0xFFFF), m * (x >> 16)
+    return (hi + (lo >> 16)) >> 16, (lo + ((hi & 0xFFFF) << 16)) & _M32
+
+
+def philox4x32_10_word0(c0, c1, c2, c3, k0, k1):
+    """Word 0 of Philox-4x32-10 for int64 counter tensors c0..c3 (values < 2^32) and a key (k0, k1)."""
+    for _ in range(10):
+        hi0, lo0 = _mul32(0xD2511F53, c0)
+        hi1, lo1 = _mul32(0xCD9E8D57, c2)
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0
+
+
+def pfc_num_sampled(B, C, rate):
+    """Cs = min(C, max(ceil(rate C), min(B, C))): the static size of a step's class subset."""
+    return min(C, max(math.ceil(rate * C), min(B, C)))
+
+
+def pfc_sample(labels, C, Cs, seed, step):
+    """The Partial FC class subset of one step, by its definition (README "Partial FC"): the batch's
+    valid labels plus the Cs - |pos| other classes with the smallest (h(c), c), h(c) = word 0 of
+    Philox-4x32-10(counter (c, 0, lo32(step), hi32(step)), key (lo32(seed), hi32(seed))).
+    -> (idx int32 [round_up(Cs, 64)] ascending with a -1 tail, slot int32 [C], lab int64 [B])."""
+    labels = labels.to(torch.int64).cpu()
+    seed, step = int(seed), int(step)
+    valid = (labels >= 0) & (labels < C)
+    is_pos = torch.zeros(C, dtype=torch.bool)
+    is_pos[labels[valid]] = True
+    c = torch.arange(C, dtype=torch.int64)
+    z = torch.zeros_like(c)
+    h = philox4x32_10_word0(c, z, z + (step & _M32), z + ((step >> 32) & _M32), seed & _M32, (seed >> 32) & _M32)
+    cand = c[~is_pos]
+    order = torch.argsort(h[~is_pos], stable=True)  # cand ascends, so a stable sort by h orders by (h, c)
+    neg = cand[order[: Cs - int(is_pos.sum())]]
+    chosen = torch.sort(torch.cat([c[is_pos], neg])).values
+    idx = torch.full(((Cs + 63) // 64 * 64,), -1, dtype=torch.int32)
+    idx[:Cs] = chosen.to(torch.int32)
+    slot = torch.full((C,), -1, dtype=torch.int32)
+    slot[chosen] = torch.arange(Cs, dtype=torch.int32)
+    lab = torch.where(valid, slot[labels.clamp(0, C - 1)].to(torch.int64), torch.full_like(labels, -1))
+    return idx, slot, lab
+
+
 def adaptive_avg_pool(x, oh, ow):
     return _nhwc(F.adaptive_avg_pool2d(_nchw(_f(x)), (oh, ow))).to(x.dtype)
 

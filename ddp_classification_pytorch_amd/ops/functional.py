@@ -1939,6 +1939,94 @@ def arcface_loss(x, weight, labels, s=30.0, m=0.5, easy_margin=True, return_logi
     return _ArcFace.apply(x, weight, labels, float(s), float(m), bool(easy_margin), bool(return_logits))
 
 
+# ----------------------------------------------------------------------------- Partial FC
+_PFC_STATE = {}
+
+
+def pfc_state(device):
+    """(seed, call counter int64[1]) of the Partial FC sampler per device.  On the GPU the counter
+    lives on the device and every sampler launch advances it there, so a replayed HIP graph draws a
+    new class subset each replay; on the CPU it is a host tensor advanced by the op."""
+    device = torch.device(device)
+    key = str(device)
+    st = _PFC_STATE.get(key)
+    if st is None:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("arcface_partial_loss: first use inside a HIP-graph capture (run an eager step first)")
+        st = _PFC_STATE[key] = (int(torch.initial_seed()) & ((1 << 63) - 1),
+                                torch.zeros(1, dtype=torch.int64, device=device))
+    return st
+
+
+class _ArcFacePartialFused(Function):
+    """Partial FC on csrc/arcface_pfc.hip: the device-side sampler picks the step's Cs classes, the
+    gathered operand pass normalises only those rows, the fused head (csrc/arcface.hip, unchanged)
+    runs on the compact operands, and one scatter pass writes the dense weight gradient (exact zeros
+    for unsampled rows).  -> (mean loss, rank among the sampled classes, idx int32 [Cs])."""
+
+    @staticmethod
+    def forward(ctx, x, weight, labels, s, m, easy, Cs):
+        k = K(x)
+        B, D = x.shape
+        C = weight.shape[0]
+        Dp = arcface_fused_dp(D)
+        seed, step = pfc_state(x.device)
+        idx, slot, lab64 = k.pfc_sample(labels.to(torch.int64).contiguous(), C, Cs, seed, step)
+        xn, xnT, inv_x = k.arcface_l2norm_t(x.contiguous(), round_up(B, 64), Dp, 1e-12)
+        wn, wnT, inv_w = k.arcface_gather_l2norm_t(weight.detach().contiguous(), idx, Dp, 1e-12)  # [Csp][Dp]
+        loss_rows, rank, lse, lab = k.arcface_fused_fwd(xn, wn, lab64, B, Cs, s, m, easy)
+        ctx.save_for_backward(xn, xnT, inv_x, wn, wnT, inv_w, lab64, lse, lab, slot)
+        ctx.cfg = (B, Cs, D, s, x.dtype == torch.bfloat16)
+        sampled = idx[:Cs]
+        ctx.mark_non_differentiable(rank, sampled)
+        ctx.set_materialize_grads(False)
+        return loss_rows.mean(), rank, sampled
+
+    @staticmethod
+    def backward(ctx, g, _grank, _gidx):
+        if g is None:
+            return (None,) * 7
+        xn, xnT, inv_x, wn, wnT, inv_w, lab64, lse, lab, slot = ctx.saved_tensors
+        B, Cs, D, s, x_bf16 = ctx.cfg
+        k = K(xn)
+        g = g.reshape(1)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = k.arcface_fused_dx(xn, wn, wnT, lab64, lse, lab, g, 1.0 / B, inv_x, B, Cs, D, s, x_bf16)
+        if ctx.needs_input_grad[1]:
+            dwc = k.arcface_fused_dw(xn, xnT, wn, lab64, lse, lab, g, 1.0 / B, inv_w, B, Cs, D, s)  # [Cs][D]
+            dw = k.arcface_scatter_rows(dwc, slot)
+        return dx, dw, None, None, None, None, None
+
+
+def arcface_partial_loss(x, weight, labels, s=30.0, m=0.5, easy_margin=True, sample_rate=0.1):
+    """Partial FC (An et al., CVPR 2022): the ArcFace loss over the step's class subset -- every
+    valid label of the batch plus random other classes up to Cs = min(C, max(ceil(sample_rate C),
+    min(B, C))) (:func:`_ref.pfc_sample` is the definition).  -> (mean loss, rank of the label among
+    the sampled classes, idx int32 [Cs]: the sampled classes, ascending).  The weight gradient is
+    dense, with exact zeros for unsampled rows.  ``sample_rate = 1.0`` runs the same path on the
+    identity subset.  On the GPU: csrc/arcface_pfc.hip + the fused head; on the CPU: the reference
+    sampler and the CPU head math on ``weight[idx]``."""
+    if (weight.dim() != 2 or weight.dtype != torch.float32 or x.dim() != 2
+            or x.dtype not in (torch.float32, torch.bfloat16) or not 1 <= x.shape[1] <= ARCFACE_FUSED_MAX_D
+            or x.shape[1] != weight.shape[1] or x.shape[0] < 1 or not 0.0 < sample_rate <= 1.0):
+        raise ValueError("arcface_partial_loss covers a 2-D fp32 weight [C, D], fp32 or bf16 features [B, D], "
+                         f"1 <= D <= {ARCFACE_FUSED_MAX_D} and 0 < sample_rate <= 1, got {x.dtype} {tuple(x.shape)}, "
+                         f"{weight.dtype} {tuple(weight.shape)}, sample_rate = {sample_rate}")
+    C = weight.shape[0]
+    Cs = _ref.pfc_num_sampled(x.shape[0], C, float(sample_rate))
+    if x.is_cuda:
+        return _ArcFacePartialFused.apply(x, weight, labels, float(s), float(m), bool(easy_margin), Cs)
+    seed, step = pfc_state(x.device)
+    idx, _, lab = _ref.pfc_sample(labels, C, Cs, seed, int(step))
+    step += 1
+    idx = idx[:Cs]
+    # index_select's backward is the index_add into the dense gradient
+    loss, rank, _ = _ArcFace.apply(x, weight.index_select(0, idx.long()), lab, float(s), float(m), bool(easy_margin),
+                                   False)
+    return loss, rank, idx
+
+
 # ----------------------------------------------------------------------------- retrieval
 KNN_MAX_K = 8
 KNN_MAX_D = 512
