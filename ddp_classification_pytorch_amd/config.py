@@ -142,6 +142,10 @@ def build_parser() -> argparse.ArgumentParser:
       help="with both alphas positive: probability of CutMix, else Mixup")
     a("--mix-mode", dest="mix_mode", default="batch", choices=["batch", "elem"],
       help="one draw per batch, or one per image")
+    # RandAugment on the device (data/randaug.py; the baseline workload with --data shards only)
+    a("--randaugment", dest="randaugment", default=None, metavar="N,M",
+      help="RandAugment: N ops per image at magnitude M of 30 (e.g. 2,9), applied to the uint8 batch by the shard "
+           "loader before Mixup / CutMix")
     # exponential moving average of the weights (optim/ema.py; baseline, arcface, cdr)
     a("--model-ema", dest="model_ema", action="store_true",
       help="keep an exponential moving average of every fp32 weight and BN statistic on the device, evaluate it "
@@ -258,6 +262,7 @@ def resolve(args: argparse.Namespace) -> argparse.Namespace:
         args.graph = (env == "1") if env in ("0", "1") else (on_gpu and args.workload in ("baseline", "arcface", "cdr"))
     if args.nested > 0 and args.dropout > 0:
         raise ValueError("nested dropout and standard dropout are mutually exclusive (NESTED/train.py:489-490)")
+    check_randaug(args)
     return args
 
 
@@ -274,6 +279,22 @@ def refuse_mix(args, workload: str):
     if given:
         raise ValueError(f"{', '.join(given)}: Mixup / CutMix is wired for --workload baseline only; the {workload} "
                          f"workload's head and loss take one label per image")
+
+
+def check_randaug(args):
+    """--randaugment N,M at start-up: a malformed value, a workload other than baseline or a --data
+    route other than the native shard loader is an error, never silently ignored."""
+    text = getattr(args, "randaugment", None)
+    if text is None:
+        return
+    from .data.randaug import parse_flag
+
+    parse_flag(text)
+    if args.workload != "baseline":
+        raise ValueError(f"--randaugment: RandAugment is wired for --workload baseline only, not {args.workload}")
+    if args.data != "shards":
+        raise ValueError(f"--randaugment: RandAugment runs on the device in the native shard loader (--data shards), "
+                         f"not --data {args.data}")
 
 
 def refuse_ema(args, workload: str):

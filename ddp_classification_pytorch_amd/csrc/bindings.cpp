@@ -1590,6 +1590,27 @@ Tensor rotate_nearest_crop(const Tensor& canvas, const Tensor& meta, const Tenso
   return out;
 }
 
+// RandAugment: uint8 [N][H][W][3] + device plan int32 [N][K][8] = {op, parameter, a0..a5} (data/randaug.py).
+// The kernel treats an op id outside 0..13 as the identity and bounds every source index itself, so
+// the plan's values need no validation here; the Python wrapper refuses them on the host plan.
+Tensor rand_augment(const Tensor& imgs, const Tensor& plan) {
+  TORCH_CHECK(imgs.is_cuda() && imgs.scalar_type() == at::kByte && imgs.dim() == 4 && imgs.size(3) == 3 &&
+                  imgs.is_contiguous(),
+              "rand_augment covers contiguous uint8 [N, H, W, 3] batches on the device");
+  const int64_t N = imgs.size(0), H = imgs.size(1), W = imgs.size(2);
+  TORCH_CHECK(plan.is_cuda() && plan.get_device() == imgs.get_device() && plan.scalar_type() == at::kInt &&
+                  plan.dim() == 3 && plan.size(0) == N && plan.size(1) >= 1 && plan.size(1) <= 4 &&
+                  plan.size(2) == 8 && plan.is_contiguous(),
+              "rand_augment covers 1 <= num_ops <= 4 as a contiguous int32 [N, num_ops, 8] plan on the images' device");
+  TORCH_CHECK(H > 0 && W > 0 && H * W * 3 <= dcp::rand_augment_max_bytes(), "rand_augment covers images of at most ",
+              dcp::rand_augment_max_bytes(), " bytes (224 x 224 x 3 fits), not ", H, " x ", W);
+  auto out = at::empty_like(imgs);
+  const int rc = dcp::launch_rand_augment(imgs.data_ptr<uint8_t>(), plan.data_ptr<int32_t>(), (int)N,
+                                          (int)plan.size(1), (int)H, (int)W, out.data_ptr<uint8_t>(), cur_stream());
+  TORCH_CHECK(rc == 0, "rand_augment refused the launch (code ", rc, ")");
+  return out;
+}
+
 Tensor to_nhwc_s2d(const Tensor& src, bool nchw, double in_scale, const optional<Tensor>& mean,
                    const optional<Tensor>& stdv, int64_t block) {
   CHECK_DEV(src);
@@ -2777,6 +2798,7 @@ TORCH_LIBRARY(dcp, m) {
         &resample_crop);
   m.def("rotate_nearest_crop(Tensor canvas, Tensor meta, Tensor geo, int Ho, int Wo) -> Tensor",
         &rotate_nearest_crop);
+  m.def("rand_augment(Tensor imgs, Tensor plan) -> Tensor", &rand_augment);
   m.def("to_nhwc_s2d(Tensor src, bool nchw, float in_scale, Tensor? mean, Tensor? std, int block=2) -> Tensor", &to_nhwc_s2d);
   m.def("to_nhwc_mix(Tensor src, bool nchw, int cpad, float in_scale, Tensor? mean, Tensor? std, Tensor partner, "
         "Tensor blend, Tensor box) -> Tensor",

@@ -427,6 +427,11 @@ int launch_resample_crop(const uint8_t* src, const int64_t* meta, const int32_t*
 // Image.rotate(NEAREST) through geo's 16.16 integers -> mirror -> window, of canvases [B][Sh][Sw][3]
 int launch_rotate_nearest_crop(const uint8_t* canvas, const int64_t* meta, const int32_t* geo, const int32_t* hgeo,
                                int B, int Sh, int Sw, int Ho, int Wo, uint8_t* out, int* bad, hipStream_t s);
+// RandAugment (randaug.hip): K ops per image from plan [N][K][8] = {op, parameter, a0..a5}, one workgroup
+// per image with the image in LDS.  Returns 0, or 1 (nothing launched) when H W 3 exceeds
+// rand_augment_max_bytes(), 2 when K is outside 1..4.
+int rand_augment_max_bytes();
+int launch_rand_augment(const uint8_t* in, const int* plan, int N, int K, int H, int W, uint8_t* out, hipStream_t s);
 void launch_act_bwd(const bf16* dy, const bf16* y, bf16* dx, size_t numel, int act, hipStream_t s);
 void launch_prefix_mask(const bf16* x, bf16* y, int B, int D, const int* keep, hipStream_t s);
 // InplaceABN effective weight: geff = |g| + eps, rg = 1 / geff; backward out = d * sign(g)

@@ -367,14 +367,17 @@ class ShardLoader:
     ``resample="pil"`` delivers the bytes of the PIL pipeline (module docstring) through
     ``dcpl_submit_exact`` and the exact kernels; the pad-crop preset keeps the affine route.
     ``tap``, when set, is called with (uint8 images, meta, xf or geo or None) of every batch before
-    normalisation: tests and tools look at the augmented bytes there.
+    normalisation: tests and tools look at the augmented bytes there.  ``randaug`` (a
+    ``data.randaug.RandAugSampler``, train loaders only) runs ``Fn.rand_augment`` on that uint8 batch
+    after the tap and before the Mixup / CutMix plan; without it no such kernel runs.
     """
 
     def __init__(self, path: str, batch_size: int, sampler=None, aug: AugSpec = None, out_size: int = 224,
                  device="cuda", threads: int = 8, prefetch: int = 3, seed: int = 0, drop_last: bool = False,
                  mean=IMAGENET_MEAN, std=IMAGENET_STD, cpad: int = 8, s2d=False, return_index: bool = False,
-                 resample: str = "fast", mix=None):
+                 resample: str = "fast", mix=None, randaug=None):
         self.mix = mix  # a data.mix.MixSampler (train loaders only)
+        self.randaug = randaug  # a data.randaug.RandAugSampler (train loaders only)
         if resample not in RESAMPLE_MODES:
             raise ValueError(f"shard resampling mode {resample!r}: one of {RESAMPLE_MODES}")
         self.gather = NativeGather(path, threads)
@@ -455,6 +458,11 @@ class ShardLoader:
             imgs = Fn.crop_resize(src, meta, self.out_size, self.out_size)
         if self.tap is not None:
             self.tap(imgs, meta, extra)
+        if self.randaug is not None:
+            # RandAugment on the uint8 batch, after crop / warp / resample (tap saw it un-augmented) and
+            # before the Mixup / CutMix plan
+            epoch = getattr(self.sampler, "epoch", self.epoch)
+            imgs = Fn.rand_augment(imgs, self.randaug.plan(B, self.out_size, self.out_size, slot["step"], epoch))
         plan = None
         if self.mix is not None:
             # Mixup / CutMix on the final uint8 batch, after crop / warp / resample (tap saw it unmixed)

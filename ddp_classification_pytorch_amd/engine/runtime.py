@@ -122,6 +122,27 @@ def _mix_sampler(args, rt):
                       mode=args.mix_mode, seed=args.seed, rank=rt.rank)
 
 
+def _randaug_sampler(args, rt):
+    """--randaugment N,M: the train shard loader's RandAugment plan sampler (data/randaug.py), keyed by
+    the seed, with the rank in every draw; None without the flag."""
+    if getattr(args, "randaugment", None) is None:
+        return None
+    from ..data.randaug import parse_flag
+
+    sampler = parse_flag(args.randaugment)
+    sampler.seed, sampler.rank = int(args.seed), int(rt.rank)
+    return sampler
+
+
+def _check_randaug_size(args, size: int):
+    from ..data.randaug import MAX_IMAGE_BYTES
+
+    if getattr(args, "randaugment", None) is not None and size * size * 3 > MAX_IMAGE_BYTES:
+        raise ValueError(f"--randaugment: rand_augment covers images of at most {MAX_IMAGE_BYTES} bytes (224 x 224 x 3 "
+                         f"fits) and this preset trains at {size} x {size}; the baseline preset trains at 256 x 256 "
+                         f"for --image-size 224, so pass another size up to 227, e.g. --image-size 192")
+
+
 def _shard_loaders(args, rt, tr, va, tr_s, va_s, mean, std, cpad, s2d, drop_last_train):
     """Native loaders (C++ gather + GPU crop/resize, or the affine warp for the presets that rotate,
     pad or stretch: CDR, CIFAR, PLC).  None -- the PIL DataLoader over the same shard -- only for a
@@ -135,11 +156,12 @@ def _shard_loaders(args, rt, tr, va, tr_s, va_s, mean, std, cpad, s2d, drop_last
         va_aug, va_size = aug_preset(args.transform, False, args.image_size, resample=resample)
     except ValueError:
         return None
+    _check_randaug_size(args, tr_size)
     idx = args.workload == "plc"
     kw = dict(device=rt.device, threads=args.loader_threads, seed=args.seed, mean=mean, std=std, cpad=cpad,
               return_index=idx, resample=resample)
     tr_l = ShardLoader(tr.path, args.batchsize, tr_s, tr_aug, tr_size, drop_last=drop_last_train,
-                       s2d=s2d, mix=_mix_sampler(args, rt), **kw)
+                       s2d=s2d, mix=_mix_sampler(args, rt), randaug=_randaug_sampler(args, rt), **kw)
     va_l = ShardLoader(va.path, args.batchsize, va_s, va_aug, va_size, s2d=s2d, **kw)
     return tr_l, va_l
 
@@ -180,6 +202,9 @@ def build_data(args, rt: Runtime, drop_last_train=False):
         native = _shard_loaders(args, rt, tr, va, tr_s, va_s, mean, std, cpad, s2d, drop_last_train)
         if native is not None:
             return native + (tr, va)
+    if getattr(args, "randaugment", None) is not None:
+        raise ValueError("--randaugment runs in the native shard loader only; this preset fell back to the PIL "
+                         "DataLoader route")
     workers = args.workers if args.data != "synthetic" else min(args.workers, 2)
     tr_l = build_loader(tr, args.batchsize, tr_s, workers=workers, drop_last=drop_last_train,
                         worker_init_fn=worker_init_fn)

@@ -2273,6 +2273,37 @@ def resample_exact(src: torch.Tensor, meta: torch.Tensor, geo: torch.Tensor, Ho:
     return resample_crop(src, meta, geo, Ho, Wo, bicubic, False)
 
 
+def rand_augment(imgs: torch.Tensor, plan) -> torch.Tensor:
+    """RandAugment of a uint8 [N, H, W, 3] batch: image n goes through the ops of row n of ``plan`` (a
+    :class:`data.randaug.RandAugPlan` on the host) and equals, byte for byte, Pillow's result
+    (``data.randaug.apply_pil``, which is also the CPU path).  On the device the plan travels as one
+    pinned buffer without a synchronisation and ``dcp::rand_augment`` (csrc/randaug.hip) runs the chain
+    with the image in LDS.  ``plan`` may also be the int32 [N, K, 8] device tensor of
+    ``data.randaug.plan_to_device`` (its op ids were checked when it was made; the kernel reads any
+    other id as the identity)."""
+    from ..data import randaug
+
+    if (not torch.is_tensor(imgs) or imgs.dtype != torch.uint8 or imgs.dim() != 4 or imgs.shape[3] != 3
+            or not imgs.is_contiguous()):
+        raise ValueError("rand_augment covers contiguous uint8 [N, H, W, 3] batches, not "
+                         f"{getattr(imgs, 'dtype', type(imgs))} {tuple(getattr(imgs, 'shape', ()))}")
+    N, H, W, _ = imgs.shape
+    if H * W * 3 > randaug.MAX_IMAGE_BYTES:
+        raise ValueError(f"rand_augment covers images of at most {randaug.MAX_IMAGE_BYTES} bytes "
+                         f"(224 x 224 x 3 fits), not {H} x {W}")
+    if torch.is_tensor(plan):
+        if plan.dim() != 3 or plan.shape[0] != N or not 1 <= plan.shape[1] <= randaug.MAX_CHAIN or plan.shape[2] != 8:
+            raise ValueError(f"rand_augment covers 1 <= num_ops <= {randaug.MAX_CHAIN} as an int32 [N, num_ops, 8] "
+                             f"packed plan, not {tuple(plan.shape)}")
+        if not imgs.is_cuda:
+            raise ValueError("rand_augment covers packed plans on the device only; the CPU path takes a RandAugPlan")
+        return K(imgs).rand_augment(imgs, plan)
+    randaug.check_plan(plan, N)
+    if not imgs.is_cuda:
+        return randaug.apply_pil_batch(imgs, plan)
+    return K(imgs).rand_augment(imgs, randaug.plan_to_device(plan, imgs.device))
+
+
 # ----------------------------------------------------------------------------- space-to-depth stem
 def nhwc_to_s2d(x: torch.Tensor) -> torch.Tensor:
     """[N, H, W, C>=4] NHWC image activations (channels >= 3 zero) -> [N, H/2, W/2, 16]."""
