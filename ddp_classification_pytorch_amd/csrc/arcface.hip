@@ -26,9 +26,9 @@
 //                                     block's complete dwn in registers, the normalisation backward
 //                                     applied in the epilogue (cross-lane dot) -> dW written once.
 //
-// The dcos register tile becomes the next MFMA's B operand without any data movement: its
-// accumulator layout (lane holds 4 consecutive rows of one column) is read as a 32-deep k-fragment
-// whose k order is a fixed permutation, and the A operand is loaded in the same permuted order.
+// The tile layouts, the LDS-DMA staging, the permuted k-fragment that lets the dcos register tile be
+// the next MFMA's B operand without any data movement, the margin and the operand normalisation are
+// in score_tile.cuh, shared with arcface_sub.hip, arcface_pfc.hip, knn.hip and knn_wide.hip.
 // Deterministic: every sum has a fixed order (no atomics).
 //
 // Widths: Dp = 128 / 256 / 512 (KS = Dp / 32 = 4 / 8 / 16).  At Dp = 512 the forward keeps 64-class
@@ -37,8 +37,8 @@
 // dcos tile is ONE 32-deep k-fragment, and run one wave per SIMD (128 accumulator + 64 fragment
 // registers per lane).  The dW kernel's per-row (label, t, dphi, lse) travels with each row tile
 // through the same DMA ring, so its LDS does not depend on the batch size.
-#include "common.cuh"
 #include "launchers.h"
+#include "score_tile.cuh"
 
 namespace dcp {
 
@@ -66,136 +66,15 @@ struct ArcParams {
   float s;
 };
 
-// margin (ARCFACE/arc_main.py:157-176), guarded at cos = +-1
-__device__ __forceinline__ void arc_margin(float c, float cos_m, float sin_m, float th, float mm, int easy, float& phi,
-                                           float& dphi) {
-  c = fminf(fmaxf(c, -1.f), 1.f);
-  const float sn = sqrtf(fminf(fmaxf(1.f - c * c, 0.f), 1.f));
-  const float p = c * cos_m - sn * sin_m;
-  const float dp = cos_m + (sn > 1e-6f ? sin_m * c / sn : 0.f);
-  if (easy) {
-    phi = c > 0.f ? p : c;
-    dphi = c > 0.f ? dp : 1.f;
-  } else {
-    phi = c > th ? p : c - mm;
-    dphi = c > th ? dp : 1.f;
-  }
-}
-
-// byte offset of 16-byte chunk c of row r in a row-major [rows][Dp] bf16 tile, XOR-swizzled
-// (16 consecutive rows at one chunk -> 16 distinct bank groups for the fragment reads)
-__device__ __forceinline__ uint32_t rm_off(uint32_t r, uint32_t c, uint32_t Dp) {
-  return r * Dp * 2u + ((c ^ (r & 15u)) << 4);
-}
-// byte offset of 8-byte half h of chunk c of row d in a [Dp][64] bf16 tile (128-byte rows)
-__device__ __forceinline__ uint32_t tr_off(uint32_t d, uint32_t c, uint32_t h) {
-  return d * 128u + ((c ^ (d & 7u)) << 4) + (h << 3);
-}
-
-// the same for a [Dp][32] tile (64-byte rows): the 4 rows d, d + 4, d + 8, d + 12 that share a 256-byte
-// bank window take 4 distinct chunks, so 16 consecutive rows at one chunk cover all 64 banks
-__device__ __forceinline__ uint32_t tr32_off(uint32_t d, uint32_t c, uint32_t h) {
-  return d * 64u + ((c ^ ((d >> 2) & 3u)) << 4) + (h << 3);
-}
-
-// LDS-DMA versions of the two stagings (one 16-byte global_load_lds per lane and instruction, the
-// lane's data landing at base + 16 lane: the swizzle is applied on the source side).  Untracked: the
-// caller waits vmcnt(0) + barrier before reading the tile.  4 waves share the tile.
-template <int DP, int TILE = kArcTile>
-__device__ __forceinline__ void dma_rm(char* T, const bf16* g, int r0, int w, int lane) {
-  constexpr int CPR = DP / 8, RPB = 64 / CPR, NI = TILE / RPB / 4;  // rows per 1 KB block; blocks per wave
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int blk = w * NI + i;
-    const int r = blk * RPB + lane / CPR, pos = lane % CPR;
-    const int c = pos ^ (r & 15);
-    dma16(g + (size_t)(r0 + r) * DP + c * 8, T + blk * 1024);
-  }
-}
-template <int DP>
-__device__ __forceinline__ void dma_tr(char* T, const bf16* g, int c0, int ld, int w, int lane) {
-  constexpr int NI = DP / 8 / 4;  // 8 rows (128 B each) per 1 KB block
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int blk = w * NI + i;
-    const int d = blk * 8 + lane / 8, pos = lane % 8;
-    const int c = pos ^ (d & 7);
-    dma16(g + (size_t)d * ld + c0 + c * 8, T + blk * 1024);
-  }
-}
-
-template <int DP>
-__device__ __forceinline__ void dma_tr32(char* T, const bf16* g, int c0, int ld, int w, int lane) {
-  constexpr int NI = DP / 16 / 4;  // 16 rows (64 B each) per 1 KB block
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int blk = w * NI + i;
-    const int d = blk * 16 + lane / 4, pos = lane % 4;
-    const int c = pos ^ ((d >> 2) & 3);
-    dma16(g + (size_t)d * ld + c0 + c * 8, T + blk * 1024);
-  }
-}
-
-// the 8 bf16 of a permuted 32-deep k-fragment from a transposed tile: k slots 8q..8q+3 <- columns
-// 32 kk + 4q .. +3, slots 8q+4..8q+7 <- columns 32 kk + 16 + 4q .. +3 (the accumulator layout of
-// two 16-wide MFMA results, read as one k-fragment)
-__device__ __forceinline__ bf16x8 tr_frag(const char* T, uint32_t d, int kk, uint32_t q) {
-  const uint32_t lo = 32u * kk + 4u * q, hi = lo + 16u;  // column indices (bf16)
-  const bf16x4 a = *LDS_PTR(const bf16x4, T + tr_off(d, lo >> 3, (lo >> 2) & 1u));
-  const bf16x4 b = *LDS_PTR(const bf16x4, T + tr_off(d, hi >> 3, (hi >> 2) & 1u));
-  return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-// the same from a [Dp][32] tile, whose 32 columns are the one k-fragment
-__device__ __forceinline__ bf16x8 tr32_frag(const char* T, uint32_t d, uint32_t q) {
-  const bf16x4 a = *LDS_PTR(const bf16x4, T + tr32_off(d, q >> 1, q & 1u));       // columns 4 q .. + 3
-  const bf16x4 b = *LDS_PTR(const bf16x4, T + tr32_off(d, 2u + (q >> 1), q & 1u));  // 16 + 4 q .. + 3
-  return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-
 }  // namespace
 
-// rows of x [R][D] (fp32 or bf16) -> normalised bf16 rows y [Rp][Dp] AND their transpose yT [Dp][Rp]
-// (zero padding in both dimensions), inverse norms [Rp]: the operands of the fused head in one pass
-// (a separate transpose launch per operand cost as much as the normalisation).  One workgroup per
-// 64 rows; each wave normalises 16 rows, the tile is transposed through LDS.
+// rows of x [R][D] (fp32 or bf16) -> the operands of the fused head (l2norm_t_tile): normalised bf16 rows
+// y [Rp][Dp], their transpose yT [Dp][Rp], inverse norms [Rp].  One workgroup per 64 rows.
 template <typename T, int DP>
 __global__ void __launch_bounds__(256) arc_l2norm_t_kernel(const T* __restrict__ x, int R, int D, int Rp,
                                                            bf16* __restrict__ y, bf16* __restrict__ yT,
                                                            float* __restrict__ inv_norm, float eps) {
-  constexpr int EPL = DP / 64;  // elements per lane of a row
-  __shared__ __attribute__((aligned(16))) bf16 tile[64][DP + 8];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int r0 = blockIdx.x * 64;
-#pragma unroll 4
-  for (int k = 0; k < 16; ++k) {
-    const int rl = w * 16 + k, r = r0 + rl;
-    float v[EPL];
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const int j = lane * EPL + e;
-      v[e] = (r < R && j < D) ? (float)x[(size_t)r * D + j] : 0.f;
-      ss += v[e] * v[e];
-    }
-    ss = wave_sum(ss);
-    const float iv = r < R ? 1.f / fmaxf(sqrtf(ss), eps) : 0.f;
-    if (lane == 0) inv_norm[r] = iv;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const bf16 b = f2bf(v[e] * iv);
-      tile[rl][lane * EPL + e] = b;
-      y[(size_t)r * DP + lane * EPL + e] = b;
-    }
-  }
-  __syncthreads();
-  // yT rows d: the 64 columns r0 .. r0 + 63 (128 contiguous bytes); a thread writes 8 columns
-  for (int e = threadIdx.x; e < DP * 8; e += 256) {
-    const int d = e >> 3, c = (e & 7) * 8;
-    bf16x8 o;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = tile[c + k][d];
-    *(bf16x8*)(yT + (size_t)d * Rp + r0 + c) = o;
-  }
+  l2norm_t_tile<DP>([=](int r) { return OperandRow<T>{r < R, x, (size_t)r}; }, D, Rp, y, yT, inv_norm, eps);
 }
 
 // per row: target logit and margin derivative (one wave per row)
@@ -233,18 +112,8 @@ __global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) arc_rows_kernel(const A
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t q = lane >> 4, l15 = lane & 15;
-  // XCD-aware (row block, split) of this workgroup: workgroups are dispatched round-robin over the 8
-  // XCDs, so the ones sharing an XCD (and its L2) take the SAME class splits for all row blocks --
-  // each XCD streams 1/8 of the weight tiles instead of all of them
-  int rb = blockIdx.x, split = blockIdx.y;
-  {
-    const int RB = gridDim.x, S = gridDim.y, L = blockIdx.x + blockIdx.y * RB;
-    if ((S & 7) == 0) {
-      const int xcd = L & 7, idx = L >> 3;
-      split = xcd * (S >> 3) + idx / RB;
-      rb = idx % RB;
-    }
-  }
+  int rb, split;  // (row block, class split)
+  xcd_row_split(rb, split);
   const int row = rb * 64 + w * 16 + (int)l15;
   // this lane's x fragments (n = row), the whole feature dimension, in VGPRs
   bf16x8 xf[KS];
@@ -281,9 +150,7 @@ __global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) arc_rows_kernel(const A
     const int c0 = tile * TILE, b = (tile - t0) & 1;
     const char* Wt = smem + b * BUF;
     const char* WT = Wt + TILE * DP * 2;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // this tile landed for every wave; the other buffer's reads are done
-    asm volatile("" ::: "memory");
+    tile_landed();  // this tile landed for every wave; the other buffer's reads are done
     if (tile + 1 < t1) stage(tile + 1, b ^ 1);
     f32x4 acc[NJ];
 #pragma unroll
@@ -372,7 +239,10 @@ __global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) arc_rows_kernel(const A
   }
 }
 
-// merge the forward splits per row: loss, label rank, lse (saved for the backward)
+// merge the forward splits per row: loss, label rank, lse (saved for the backward).  A label is valid as
+// the calling head's other kernels see it: the plain head reads it as int, the sub-centre head (LABEL64)
+// compares all 64 bits.
+template <bool LABEL64>
 __global__ void __launch_bounds__(256) arc_fwd_finalize_kernel(const float* __restrict__ part, int S, int B, int Bp,
                                                                int C, const int64_t* __restrict__ labels,
                                                                const float* __restrict__ lab,
@@ -393,7 +263,7 @@ __global__ void __launch_bounds__(256) arc_fwd_finalize_kernel(const float* __re
   const float cnt = wave_sum(v[2]);
   if (lane == 0) {
     const float l = M + __logf(sum);
-    const int y = (int)labels[r];
+    const int64_t y = LABEL64 ? labels[r] : (int64_t)(int)labels[r];
     const bool valid = y >= 0 && y < C;
     lse[r] = l;
     loss[r] = valid ? l - lab[2 * r] : 0.f;
@@ -499,9 +369,7 @@ __global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) arc_dw_kernel(const Arc
     const char* Xt = smem + b * BUF;
     const char* XT = Xt + TILE * DP * 2;
     const float* info = (const float*)(Xt + TB);  // [TILE][4]
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // this row tile landed for every wave; the other buffer is free
-    asm volatile("" ::: "memory");
+    tile_landed();  // this row tile landed for every wave; the other buffer is free
     if (r0 + TILE < rend) stage(r0 + TILE, b ^ 1);
     f32x4 acc[NJ];
 #pragma unroll
@@ -572,22 +440,22 @@ __global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) arc_dw_kernel(const Arc
 
 // ---------------------------------------------------------------------------
 namespace {
-int arc_splits(int blocks, int ntiles, int target, int cap) {
-  int s = (target + blocks - 1) / std::max(1, blocks);
-  s = std::max(1, std::min(s, std::min(ntiles, cap)));
-  return s;
-}
-template <int KS>
-void set_lds(const void* f, size_t bytes) {
-  (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-bool arc_dp_ok(int Dp) { return Dp == 128 || Dp == 256 || Dp == 512; }
 constexpr size_t kArcLdsMax = 160 * 1024;  // one workgroup may take the whole CU's LDS
 }  // namespace
 
+void launch_arc_fwd_finalize(const float* part, int S, int B, int Bp, int C, const int64_t* labels, const float* lab,
+                             float* loss, int* rank, float* lse, bool label64, hipStream_t st) {
+  if (label64)
+    hipLaunchKernelGGL(arc_fwd_finalize_kernel<true>, dim3(Bp / 4), dim3(256), 0, st, part, S, B, Bp, C, labels, lab,
+                       loss, rank, lse);
+  else
+    hipLaunchKernelGGL(arc_fwd_finalize_kernel<false>, dim3(Bp / 4), dim3(256), 0, st, part, S, B, Bp, C, labels, lab,
+                       loss, rank, lse);
+}
+
 bool launch_arcface_l2norm_t(const void* x, bool is_bf16, int R, int D, int Rp, int Dp, bf16* y, bf16* yT, float* inv,
                              float eps, hipStream_t st) {
-  if (Rp % 64 || Rp < R || D > Dp || !arc_dp_ok(Dp)) return false;
+  if (Rp % 64 || Rp < R || D > Dp || !score_dp_ok(Dp)) return false;
 #define ARC_NT(T_, DP_) \
   hipLaunchKernelGGL((arc_l2norm_t_kernel<T_, DP_>), dim3(Rp / 64), dim3(256), 0, st, (const T_*)x, R, D, Rp, y, yT, inv, eps);
   if (is_bf16) {
@@ -600,18 +468,16 @@ bool launch_arcface_l2norm_t(const void* x, bool is_bf16, int R, int D, int Rp, 
 }
 
 int arcface_fused_fwd_splits(int Bp, int Cp) {
-  const int s = arc_splits(Bp / 64, Cp / kArcTile, 1024, 64);
-  return s >= 8 ? s / 8 * 8 : s;
+  return score_splits(Bp / 64, Cp / kArcTile, 1024, 64);
 }
 int arcface_fused_dx_splits(int Bp, int Cp) {
-  const int s = arc_splits(Bp / 64, Cp / kArcTile, 256, 16);
-  return s >= 8 ? s / 8 * 8 : s;  // multiples of 8: the XCD-aware split mapping
+  return score_splits(Bp / 64, Cp / kArcTile, 256, 16);
 }
 
 bool launch_arcface_fused_fwd(const bf16* xn, const bf16* wn, const int64_t* labels, int B, int Bp, int C, int Cp,
                               int Dp, float s, float m, int easy, float* lab, float* part, float* loss, int* rank,
                               float* lse, hipStream_t st) {
-  if (Bp % 64 || Cp % kArcTile || !arc_dp_ok(Dp)) return false;
+  if (Bp % 64 || Cp % kArcTile || !score_dp_ok(Dp)) return false;
   const float cm = cosf(m), sm = sinf(m), th = cosf(3.14159265358979f - m), mm = sinf(3.14159265358979f - m) * m;
   hipLaunchKernelGGL(arc_label_kernel, dim3(Bp / 4), dim3(256), 0, st, xn, wn, labels, B, Bp, C, Dp, s, cm, sm, th, mm,
                      easy, lab);
@@ -624,12 +490,11 @@ bool launch_arcface_fused_fwd(const bf16* xn, const bf16* wn, const int64_t* lab
   if (lds > kArcLdsMax) return false;
   const dim3 grid(Bp / 64, p.S);
 #define ARC_FWD(KS_)                                                                                   \
-  set_lds<KS_>((const void*)arc_rows_kernel<KS_, 0>, lds);                                            \
+  score_set_lds((const void*)arc_rows_kernel<KS_, 0>, lds);                                            \
   hipLaunchKernelGGL((arc_rows_kernel<KS_, 0>), grid, dim3(256), lds, st, p);
   if (Dp == 128) { ARC_FWD(4) } else if (Dp == 256) { ARC_FWD(8) } else { ARC_FWD(16) }
 #undef ARC_FWD
-  hipLaunchKernelGGL(arc_fwd_finalize_kernel, dim3(Bp / 4), dim3(256), 0, st, part, p.S, B, Bp, C, labels,
-                     lab, loss, rank, lse);
+  launch_arc_fwd_finalize(part, p.S, B, Bp, C, labels, lab, loss, rank, lse, false, st);
   return true;
 }
 
@@ -637,7 +502,7 @@ bool launch_arcface_fused_dx(const bf16* xn, const bf16* wn, const bf16* wnT, co
                              int C, int Cp, int Dp, int D, float s, const float* lab, const float* lse,
                              const float* gout, float scale, const float* inv_x, float* part, void* dx, bool dx_bf16,
                              hipStream_t st) {
-  if (Bp % 64 || Cp % kArcTile || !arc_dp_ok(Dp) || D > Dp) return false;
+  if (Bp % 64 || Cp % kArcTile || !score_dp_ok(Dp) || D > Dp) return false;
   ArcParams p{};
   p.xn = xn; p.wn = wn; p.wnT = wnT; p.labels = labels; p.lab = lab; p.lse = lse; p.gout = gout; p.part = part;
   p.scale = scale; p.B = B; p.Bp = Bp; p.C = C; p.Cp = Cp; p.Dp = Dp; p.s = s;
@@ -648,7 +513,7 @@ bool launch_arcface_fused_dx(const bf16* xn, const bf16* wn, const bf16* wnT, co
   if (lds > kArcLdsMax) return false;
   const dim3 grid(Bp / 64, p.S);
 #define ARC_DX(KS_)                                                                                    \
-  set_lds<KS_>((const void*)arc_rows_kernel<KS_, 1>, lds);                                            \
+  score_set_lds((const void*)arc_rows_kernel<KS_, 1>, lds);                                            \
   hipLaunchKernelGGL((arc_rows_kernel<KS_, 1>), grid, dim3(256), lds, st, p);
   if (Dp == 128) { ARC_DX(4) } else if (Dp == 256) { ARC_DX(8) } else { ARC_DX(16) }
 #undef ARC_DX
@@ -673,7 +538,7 @@ bool launch_arcface_fused_dw(const bf16* xn, const bf16* xnT, const bf16* wn, co
                              int C, int Cp, int Dp, int D, float s, const float* lab, const float* lse,
                              const float* gout, float scale, const float* inv_w, float* part, float* info,
                              float* dw, hipStream_t st) {
-  if (Bp % 64 || Cp % kArcTile || !arc_dp_ok(Dp) || D > Dp) return false;
+  if (Bp % 64 || Cp % kArcTile || !score_dp_ok(Dp) || D > Dp) return false;
   ArcParams p{};
   p.xn = xn; p.xnT = xnT; p.wn = wn; p.labels = labels; p.lab = lab; p.lse = lse; p.gout = gout;
   p.scale = scale; p.B = B; p.Bp = Bp; p.C = C; p.Cp = Cp; p.Dp = Dp; p.s = s;
@@ -686,7 +551,7 @@ bool launch_arcface_fused_dw(const bf16* xn, const bf16* xnT, const bf16* wn, co
   if (lds > kArcLdsMax) return false;
   hipLaunchKernelGGL(arc_rowinfo_kernel, dim3((Bp + 255) / 256), dim3(256), 0, st, labels, lab, lse, B, Bp, C, info);
 #define ARC_DW(KS_)                                                                                    \
-  set_lds<KS_>((const void*)arc_dw_kernel<KS_>, lds);                                                 \
+  score_set_lds((const void*)arc_dw_kernel<KS_>, lds);                                                 \
   hipLaunchKernelGGL((arc_dw_kernel<KS_>), dim3(Cp / 64, p.S), dim3(256), lds, st, p, inv_w, D, dw);
   if (Dp == 128) { ARC_DW(4) } else if (Dp == 256) { ARC_DW(8) } else { ARC_DW(16) }
 #undef ARC_DW

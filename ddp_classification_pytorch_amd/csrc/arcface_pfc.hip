@@ -26,11 +26,10 @@
 //             pfc_write_kernel        per chunk: block scan of the packed per-thread counts, then the
 //                                     ordered write: idx[position] = c, slot[c] = position or -1
 //             pfc_relabel_kernel      lab'[b] = slot[labels[b]] (-1 for an invalid label)
-//   operand   arc_gather_l2norm_t_kernel   arc_l2norm_t_kernel (arcface.hip) with row r read from
-//                                     W[idx[r]]: the same element-to-lane mapping, wave_sum,
-//                                     1 / max(sqrt(ss), eps) and single rounding to bf16, so a compact
-//                                     row has the bits the full pass gives for that class; rows with
-//                                     idx = -1 are zero.  Reads Cs rows of W, nothing else of [C, D]
+//   operand   arc_gather_l2norm_t_kernel   l2norm_t_tile (score_tile.cuh), as arc_l2norm_t_kernel, with
+//                                     row r read from W[idx[r]]: a compact row has the bits the full
+//                                     pass gives for that class; rows with idx = -1 are zero.  Reads
+//                                     Cs rows of W, nothing else of [C, D]
 //   head      launch_arcface_fused_fwd / _dx / _dw (arcface.hip, unchanged) on the compact operands
 //             with lab' and C := Cs
 //   scatter   arc_scatter_rows_kernel one wave per output row of the dense dW [C, D]: copies compact
@@ -42,8 +41,8 @@
 //   pfc_scan_kernel        VGPR 33, LDS 32 B        pfc_clear / _mark / _relabel  VGPR <= 6, LDS 0
 //   arc_gather_l2norm_t_kernel<128 / 256 / 512>  VGPR 34 / 38 / 42, LDS 17 / 33 / 65 KB
 //   arc_scatter_rows_kernel<1 / 4>  VGPR 12 / 16, LDS 0
-#include "common.cuh"
 #include "launchers.h"
+#include "score_tile.cuh"
 
 namespace dcp {
 
@@ -288,55 +287,24 @@ bool launch_pfc_sample(const int64_t* labels, int B, int C, int Cs, uint64_t see
 }
 
 // ---------------------------------------------------------------------------
-// rows W[idx[r]] of w [C][D] fp32 -> normalised bf16 rows y [Rp][DP], their transpose yT [DP][Rp],
-// inverse norms [Rp]; idx [Rp], -1 (or anything outside [0, C)) gives a zero row.  The per-row
-// arithmetic is arc_l2norm_t_kernel's (arcface.hip), statement for statement.
+// rows W[idx[r]] of w [C][D] fp32 -> the operands l2norm_t_tile makes of them: y [Rp][DP], yT [DP][Rp],
+// inverse norms [Rp]; idx [Rp], -1 (or anything outside [0, C)) gives a zero row.
 template <int DP>
 __global__ void __launch_bounds__(256) arc_gather_l2norm_t_kernel(const float* __restrict__ w, const int* __restrict__ idx,
                                                                   int C, int D, int Rp, bf16* __restrict__ y,
                                                                   bf16* __restrict__ yT, float* __restrict__ inv_norm,
                                                                   float eps) {
-  constexpr int EPL = DP / 64;  // elements per lane of a row
-  __shared__ __attribute__((aligned(16))) bf16 tile[64][DP + 8];
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int r0 = blockIdx.x * 64;
-#pragma unroll 4
-  for (int k = 0; k < 16; ++k) {
-    const int rl = wv * 16 + k, r = r0 + rl;
-    const int src = idx[r];
-    const bool on = src >= 0 && src < C;
-    float v[EPL];
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const int j = lane * EPL + e;
-      v[e] = (on && j < D) ? w[(size_t)src * D + j] : 0.f;
-      ss += v[e] * v[e];
-    }
-    ss = wave_sum(ss);
-    const float iv = on ? 1.f / fmaxf(sqrtf(ss), eps) : 0.f;
-    if (lane == 0) inv_norm[r] = iv;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const bf16 b = f2bf(v[e] * iv);
-      tile[rl][lane * EPL + e] = b;
-      y[(size_t)r * DP + lane * EPL + e] = b;
-    }
-  }
-  __syncthreads();
-  // yT rows d: the 64 columns r0 .. r0 + 63 (128 contiguous bytes); a thread writes 8 columns
-  for (int e = threadIdx.x; e < DP * 8; e += 256) {
-    const int d = e >> 3, c = (e & 7) * 8;
-    bf16x8 o;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) o[k] = tile[c + k][d];
-    *(bf16x8*)(yT + (size_t)d * Rp + r0 + c) = o;
-  }
+  l2norm_t_tile<DP>(
+      [=](int r) {
+        const int src = idx[r];
+        return OperandRow<float>{src >= 0 && src < C, w, (size_t)src};
+      },
+      D, Rp, y, yT, inv_norm, eps);
 }
 
 bool launch_arcface_gather_l2norm_t(const float* w, const int* idx, int C, int D, int Rp, int Dp, bf16* y, bf16* yT,
                                     float* inv, float eps, hipStream_t st) {
-  if (Rp < 64 || Rp % 64 || D < 1 || D > Dp || (Dp != 128 && Dp != 256 && Dp != 512)) return false;
+  if (Rp < 64 || Rp % 64 || D < 1 || D > Dp || !score_dp_ok(Dp)) return false;
 #define ARC_GT(DP_) \
   hipLaunchKernelGGL((arc_gather_l2norm_t_kernel<DP_>), dim3(Rp / 64), dim3(256), 0, st, w, idx, C, D, Rp, y, yT, inv, eps);
   if (Dp == 128) { ARC_GT(128) } else if (Dp == 256) { ARC_GT(256) } else { ARC_GT(512) }

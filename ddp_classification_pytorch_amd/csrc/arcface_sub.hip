@@ -1,7 +1,8 @@
 // Fused Sub-center ArcFace head (Deng et al., ECCV 2020): K centres per class, a sample scored against
-// the nearest centre of each class, nothing [B, C K] in memory.  The K = 1 head is arcface.hip; this
-// file follows its scheme (cosine tiles live in v_mfma_f32_16x16x32_bf16 accumulators only, weight /
-// row tiles come through LDS by LDS-DMA, XOR-swizzled, double buffered; no atomics, fixed sum orders).
+// the nearest centre of each class, nothing [B, C K] in memory.  The K = 1 head is arcface.hip; both
+// are built on the streamed tile of score_tile.cuh (cosine tiles live in v_mfma_f32_16x16x32_bf16
+// accumulators only, weight / row tiles come through LDS by LDS-DMA, XOR-swizzled, double buffered; no
+// atomics, fixed sum orders), which also holds the margin and the operand normalisation.
 //
 // Operand layout, sub-centre-planar.  KP = 2 planes for K = 2, 4 planes for K = 3 and 4 (K = 3 carries
 // one all-zero plane).  A staged tile is 64 operand rows = G = 4 / KP class groups x KP planes x 16
@@ -18,7 +19,7 @@
 //             arcs_rows_kernel<0>     streams tiles, max over the K planes in registers, t substituted
 //                                     at the label class, online (max, sum, rank count) per (split, row):
 //                                     4 G logits per lane and tile, so 1 / K of the K = 1 head's exps
-//             arcs_fwd_finalize       merges the splits: loss, rank, lse
+//             arc_fwd_finalize        (arcface.hip) merges the splits: loss, rank, lse
 //   backward  arcs_rows_kernel<1>     recomputes the tile, dcbar = g s (softmax - onehot) (dphi at the
 //                                     label), written into the winning plane's slot of the 32-deep
 //                                     k-fragment of the second MFMA and zeros into the others (the
@@ -42,8 +43,8 @@
 // and (K - 1) 64 B read per lane and tile beside 1 KB of fragment reads, and one more barrier per tile.
 //
 // Widths: Dp = 128 / 256 (KS = 4 / 8).  LDS: 64 KB (forward), 128 KB (dX), 146 KB (dW) at Dp = 256.
-#include "common.cuh"
 #include "launchers.h"
+#include "score_tile.cuh"
 
 namespace dcp {
 
@@ -77,115 +78,22 @@ struct SubParams {
   float s;
 };
 
-// margin, guarded at cos = +-1 (the K = 1 head's arc_margin)
-__device__ __forceinline__ void sub_margin(float c, float cos_m, float sin_m, float th, float mm, int easy,
-                                           float& phi, float& dphi) {
-  c = fminf(fmaxf(c, -1.f), 1.f);
-  const float sn = sqrtf(fminf(fmaxf(1.f - c * c, 0.f), 1.f));
-  const float p = c * cos_m - sn * sin_m;
-  const float dp = cos_m + (sn > 1e-6f ? sin_m * c / sn : 0.f);
-  if (easy) {
-    phi = c > 0.f ? p : c;
-    dphi = c > 0.f ? dp : 1.f;
-  } else {
-    phi = c > th ? p : c - mm;
-    dphi = c > th ? dp : 1.f;
-  }
-}
-
-// byte offset of 16-byte chunk c of row r in a row-major [64][Dp] bf16 tile, XOR-swizzled
-__device__ __forceinline__ uint32_t rm_off(uint32_t r, uint32_t c, uint32_t Dp) {
-  return r * Dp * 2u + ((c ^ (r & 15u)) << 4);
-}
-// byte offset of 8-byte half h of chunk c of row d in a [Dp][64] bf16 tile (128-byte rows)
-__device__ __forceinline__ uint32_t tr_off(uint32_t d, uint32_t c, uint32_t h) {
-  return d * 128u + ((c ^ (d & 7u)) << 4) + (h << 3);
-}
-// LDS-DMA stagings of the two tiles (the swizzle applied on the source side; untracked: the caller
-// waits vmcnt(0) + barrier before reading).  4 waves share a tile.
-template <int DP>
-__device__ __forceinline__ void dma_rm(char* T, const bf16* g, int r0, int w, int lane) {
-  constexpr int CPR = DP / 8, RPB = 64 / CPR, NI = kTile / RPB / 4;  // rows per 1 KB block; blocks per wave
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int blk = w * NI + i;
-    const int r = blk * RPB + lane / CPR, pos = lane % CPR;
-    const int c = pos ^ (r & 15);
-    dma16(g + (size_t)(r0 + r) * DP + c * 8, T + blk * 1024);
-  }
-}
-template <int DP>
-__device__ __forceinline__ void dma_tr(char* T, const bf16* g, int c0, int ld, int w, int lane) {
-  constexpr int NI = DP / 8 / 4;  // 8 rows (128 B each) per 1 KB block
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int blk = w * NI + i;
-    const int d = blk * 8 + lane / 8, pos = lane % 8;
-    const int c = pos ^ (d & 7);
-    dma16(g + (size_t)d * ld + c0 + c * 8, T + blk * 1024);
-  }
-}
-// the 8 bf16 of a permuted 32-deep k-fragment from a transposed tile: k slots 8q..8q+3 <- columns
-// 32 kk + 4q .. +3, slots 8q+4..8q+7 <- columns 32 kk + 16 + 4q .. +3 (the accumulator layout of two
-// 16-wide MFMA results, read as one k-fragment)
-__device__ __forceinline__ bf16x8 tr_frag(const char* T, uint32_t d, int kk, uint32_t q) {
-  const uint32_t lo = 32u * kk + 4u * q, hi = lo + 16u;
-  const bf16x4 a = *LDS_PTR(const bf16x4, T + tr_off(d, lo >> 3, (lo >> 2) & 1u));
-  const bf16x4 b = *LDS_PTR(const bf16x4, T + tr_off(d, hi >> 3, (hi >> 2) & 1u));
-  return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-
-__device__ __forceinline__ void tile_landed() {
-  asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 }  // namespace
 
-// W [C][K][D] fp32 -> normalised bf16 rows y [Wp][Dp] in the planar order, yT [Dp][Wp], inverse norms
-// [Wp] (zero for padding rows).  One workgroup per tile; wave w normalises (group, plane) w.
+// W [C][K][D] fp32 -> the operands l2norm_t_tile makes of its rows in the planar order: y [Wp][Dp],
+// yT [Dp][Wp], inverse norms [Wp] (zero for padding rows).  One workgroup per tile; operand row
+// 64 t + 16 (g KP + k) + i is centre k of class CT t + 16 g + i (the inverse of sub_row).
 template <int DP>
 __global__ void __launch_bounds__(256) arcs_l2norm_t_kernel(const float* __restrict__ W, int C, int K, int D, int Wp,
                                                             bf16* __restrict__ y, bf16* __restrict__ yT,
                                                             float* __restrict__ inv_norm, float eps) {
-  constexpr int EPL = DP / 64;
-  __shared__ __attribute__((aligned(16))) bf16 tile[64][DP + 8];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int KP = sub_kp(K), CT = 64 / KP;
-  const int r0 = blockIdx.x * 64;
-  const int k = w % KP, cbase = blockIdx.x * CT + (w / KP) * 16;
-#pragma unroll 4
-  for (int cl = 0; cl < 16; ++cl) {
-    const int rl = w * 16 + cl, c = cbase + cl;
-    const bool on = c < C && k < K;
-    const float* src = W + ((size_t)c * K + k) * D;
-    float v[EPL];
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const int j = lane * EPL + e;
-      v[e] = (on && j < D) ? src[j] : 0.f;
-      ss += v[e] * v[e];
-    }
-    ss = wave_sum(ss);
-    const float iv = on ? 1.f / fmaxf(sqrtf(ss), eps) : 0.f;
-    if (lane == 0) inv_norm[r0 + rl] = iv;
-#pragma unroll
-    for (int e = 0; e < EPL; ++e) {
-      const bf16 b = f2bf(v[e] * iv);
-      tile[rl][lane * EPL + e] = b;
-      y[(size_t)(r0 + rl) * DP + lane * EPL + e] = b;
-    }
-  }
-  __syncthreads();
-  for (int e = threadIdx.x; e < DP * 8; e += 256) {
-    const int d = e >> 3, c = (e & 7) * 8;
-    bf16x8 o;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) o[u] = tile[c + u][d];
-    *(bf16x8*)(yT + (size_t)d * Wp + r0 + c) = o;
-  }
+  l2norm_t_tile<DP>(
+      [=](int r) {
+        const int p = (r & 63) >> 4, k = p % KP, c = (r >> 6) * CT + (p / KP) * 16 + (r & 15);
+        return OperandRow<float>{c < C && k < K, W, (size_t)c * K + k};
+      },
+      D, Wp, y, yT, inv_norm, eps);
 }
 
 // per row: the K cosines of the label class, their first maximum, target logit, margin derivative
@@ -215,7 +123,7 @@ __global__ void __launch_bounds__(256) arcs_label_kernel(const bf16* __restrict_
     }
   if (lane == 0) {
     float phi = 0.f, dphi = 0.f;
-    if (valid) sub_margin(best, cos_m, sin_m, th, mm, easy, phi, dphi);
+    if (valid) arc_margin(best, cos_m, sin_m, th, mm, easy, phi, dphi);
     lab[2 * r] = valid ? s * phi : 0.f;
     lab[2 * r + 1] = valid ? dphi : 0.f;
     sub[r] = bk;
@@ -233,17 +141,8 @@ __global__ void __launch_bounds__(256, 2) arcs_rows_kernel(const SubParams p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t q = lane >> 4, l15 = lane & 15;
-  // XCD-aware (row block, split): the workgroups of one XCD take the same class splits for all row
-  // blocks, so each L2 streams 1 / 8 of the weight tiles
-  int rb = blockIdx.x, split = blockIdx.y;
-  {
-    const int RB = gridDim.x, S = gridDim.y, L = blockIdx.x + blockIdx.y * RB;
-    if ((S & 7) == 0) {
-      const int xcd = L & 7, idx = L >> 3;
-      split = xcd * (S >> 3) + idx / RB;
-      rb = idx % RB;
-    }
-  }
+  int rb, split;  // (row block, class split)
+  xcd_row_split(rb, split);
   const int row = rb * 64 + w * 16 + (int)l15;
   bf16x8 xf[KS];
 #pragma unroll
@@ -377,33 +276,6 @@ __global__ void __launch_bounds__(256, 2) arcs_rows_kernel(const SubParams p) {
     float* o = p.part + ((size_t)split * p.Bp + row) * DP + 4 * q;
 #pragma unroll
     for (int f = 0; f < DF; ++f) *(f32x4*)(o + 16 * f) = dacc[f];
-  }
-}
-
-// merge the forward splits per row (one wave per row, one lane per split, S <= 64)
-__global__ void __launch_bounds__(256) arcs_fwd_finalize_kernel(const float* __restrict__ part, int S, int B, int Bp,
-                                                                int C, const int64_t* __restrict__ labels,
-                                                                const float* __restrict__ lab,
-                                                                float* __restrict__ loss, int* __restrict__ rank,
-                                                                float* __restrict__ lse) {
-  const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (r >= Bp) return;
-  if (r >= B) {  // padding rows: a defined lse for the backward kernels (their gradient is zero)
-    if (lane == 0) lse[r] = 0.f;
-    return;
-  }
-  f32x4 v = f32x4{-INFINITY, 0.f, 0.f, 0.f};
-  if (lane < S) v = *(const f32x4*)(part + ((size_t)lane * Bp + r) * 4);
-  const float M = wave_max(v[0]);
-  const float sum = wave_sum(v[0] > -INFINITY ? v[1] * __expf(v[0] - M) : 0.f);
-  const float cnt = wave_sum(v[2]);
-  if (lane == 0) {
-    const float l = M + __logf(sum);
-    const int64_t y = labels[r];
-    const bool valid = y >= 0 && y < C;
-    lse[r] = l;
-    loss[r] = valid ? l - lab[2 * r] : 0.f;
-    rank[r] = (int)cnt;
   }
 }
 
@@ -574,9 +446,6 @@ __global__ void __launch_bounds__(256, 2) arcs_dw_kernel(const SubParams p, cons
 // ---------------------------------------------------------------------------
 namespace {
 bool sub_ok(int K, int Dp) { return K >= 2 && K <= 4 && (Dp == 128 || Dp == 256); }
-void set_lds(const void* f, size_t bytes) {
-  (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
 // F(KS, K) for the runtime (Dp, K)
 #define ARCS_DISPATCH(F)                                                                              \
   if (Dp == 128) {                                                                                    \
@@ -617,12 +486,11 @@ bool launch_arcface_sub_fwd(const bf16* xn, const bf16* wn, const int64_t* label
   const size_t lds = (size_t)kTile * Dp * 2 * 2;
   const dim3 grid(Bp / 64, p.S);
 #define ARCS_FWD(KS_, K_)                                                                             \
-  set_lds((const void*)arcs_rows_kernel<KS_, K_, 0>, lds);                                            \
+  score_set_lds((const void*)arcs_rows_kernel<KS_, K_, 0>, lds);                                      \
   hipLaunchKernelGGL((arcs_rows_kernel<KS_, K_, 0>), grid, dim3(256), lds, st, p);
   ARCS_DISPATCH(ARCS_FWD)
 #undef ARCS_FWD
-  hipLaunchKernelGGL(arcs_fwd_finalize_kernel, dim3(Bp / 4), dim3(256), 0, st, part, p.S, B, Bp, C, labels, lab,
-                     loss, rank, lse);
+  launch_arc_fwd_finalize(part, p.S, B, Bp, C, labels, lab, loss, rank, lse, true, st);
   return true;
 }
 
@@ -639,7 +507,7 @@ bool launch_arcface_sub_dx(const bf16* xn, const bf16* wn, const bf16* wnT, cons
   const size_t lds = (size_t)kTile * Dp * 2 * 2 * 2;
   const dim3 grid(Bp / 64, p.S);
 #define ARCS_DX(KS_, K_)                                                                              \
-  set_lds((const void*)arcs_rows_kernel<KS_, K_, 1>, lds);                                            \
+  score_set_lds((const void*)arcs_rows_kernel<KS_, K_, 1>, lds);                                      \
   hipLaunchKernelGGL((arcs_rows_kernel<KS_, K_, 1>), grid, dim3(256), lds, st, p);
   ARCS_DISPATCH(ARCS_DX)
 #undef ARCS_DX
@@ -667,7 +535,7 @@ bool launch_arcface_sub_dw(const bf16* xn, const bf16* xnT, const bf16* wn, cons
   hipLaunchKernelGGL(arcs_rowinfo_kernel, dim3((Bp + 255) / 256), dim3(256), 0, st, labels, lab, sub, lse, B, Bp, C,
                      info);
 #define ARCS_DW(KS_, K_)                                                                              \
-  set_lds((const void*)arcs_dw_kernel<KS_, K_>, lds);                                                 \
+  score_set_lds((const void*)arcs_dw_kernel<KS_, K_>, lds);                                           \
   hipLaunchKernelGGL((arcs_dw_kernel<KS_, K_>), dim3(p.Wp / 64, p.S), dim3(256), lds, st, p, inv_w, D, dw);
   ARCS_DISPATCH(ARCS_DW)
 #undef ARCS_DW

@@ -1,7 +1,6 @@
 // Fused cosine / dot-product top-k retrieval: for every query row the k (1..8) gallery rows of largest
 // score, nothing [Nq, Ng] in memory.  The score tiles live in v_mfma_f32_16x16x32_bf16 accumulators
-// only (the skeleton of arc_rows_kernel<KS, 0> in arcface.hip) and are consumed there by a register
-// top-k selection.
+// only (the streamed tile of score_tile.cuh) and are consumed there by a register top-k selection.
 //
 // Order, everywhere: score descending, then gallery index ascending (the first of equal scores wins).
 // Never a candidate: a gallery index >= Ng (zero padding), the query's exclude[r], a NaN score.
@@ -9,7 +8,7 @@
 // does not depend on the number of gallery splits.
 //
 //   operands  knn_prep_kernel       x [R][D] fp32 / bf16 -> bf16 rows [Rp][Dp], zero padded; L2-normalised
-//                                   with the arithmetic of arc_l2norm_t_kernel (same bits) or converted
+//                                   by norm_row (score_tile.cuh: the ArcFace operands' bits) or converted
 //   select    knn_rows_kernel       grid (query blocks of 64, S gallery splits), XCD-aware for S % 8 == 0.
 //                                   4 waves x 16 query rows, fragments in VGPRs for the whole kernel;
 //                                   64-row gallery tiles through a double-buffered LDS-DMA ring.  After
@@ -49,8 +48,8 @@
 // The occupancy is the smaller of the two columns (one workgroup is one wave per SIMD): registers bind
 // at Dp = 128 for KMAX 4 and 8, LDS everywhere else.
 // Scratch is 0 in every instantiation.
-#include "common.cuh"
 #include "launchers.h"
+#include "score_tile.cuh"
 
 namespace dcp {
 
@@ -66,25 +65,6 @@ struct KnnParams {
   int* pidx;           // [S][Nqp][KMAX]
   int Nq, Nqp, Ng, Ngp, tps;
 };
-
-// byte offset of 16-byte chunk c of row r in a row-major [64][Dp] bf16 tile, XOR-swizzled
-// (16 consecutive rows at one chunk -> 16 distinct bank groups for the fragment reads)
-__device__ __forceinline__ uint32_t rm_off(uint32_t r, uint32_t c, uint32_t Dp) {
-  return r * Dp * 2u + ((c ^ (r & 15u)) << 4);
-}
-// LDS-DMA staging of a tile (one 16-byte global_load_lds per lane and instruction, the swizzle applied
-// on the source side; untracked: the caller waits vmcnt(0) + barrier before reading).  4 waves share it.
-template <int DP>
-__device__ __forceinline__ void dma_rm(char* T, const bf16* g, int r0, int w, int lane) {
-  constexpr int CPR = DP / 8, RPB = 64 / CPR, NI = kKnnTile / RPB / 4;  // rows per 1 KB block; blocks per wave
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int blk = w * NI + i;
-    const int r = blk * RPB + lane / CPR, pos = lane % CPR;
-    const int c = pos ^ (r & 15);
-    dma16(g + (size_t)(r0 + r) * DP + c * 8, T + blk * 1024);
-  }
-}
 
 // the full order: score descending, index ascending ((-inf, -1) entries after everything)
 __device__ __forceinline__ bool knn_before(float sa, int ia, float sb, int ib) {
@@ -128,30 +108,27 @@ template <> struct BfVec<8> { typedef bf16x8 type; };
 
 }  // namespace
 
-// rows of x [R][D] (fp32 or bf16) -> bf16 rows y [Rp][DP], zero padded in both dimensions; NORM: each row
-// times 1 / max(|row|, eps), summed and rounded as arc_l2norm_t_kernel does.  One wave per row.
+// rows of x [R][D] (fp32 or bf16) -> bf16 rows y [Rp][DP], zero padded in both dimensions; NORM: norm_row,
+// so a row has the bits arc_l2norm_t_kernel gives it.  One wave per row.
 template <typename T, int DP, bool NORM>
 __global__ void __launch_bounds__(256) knn_prep_kernel(const T* __restrict__ x, int R, int D, int Rp,
                                                        bf16* __restrict__ y, float eps) {
   constexpr int EPL = DP / 64;  // elements per lane of a row
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (r >= Rp) return;
-  float v[EPL];
-  float ss = 0.f;
-#pragma unroll
-  for (int e = 0; e < EPL; ++e) {
-    const int j = lane * EPL + e;
-    v[e] = (r < R && j < D) ? (float)x[(size_t)r * D + j] : 0.f;
-    ss += v[e] * v[e];
-  }
-  float iv = 1.f;
+  bf16 b[EPL];
   if constexpr (NORM) {
-    ss = wave_sum(ss);
-    iv = r < R ? 1.f / fmaxf(sqrtf(ss), eps) : 0.f;
+    norm_row<EPL>(x, r, r < R, D, lane, eps, b);
+  } else {
+#pragma unroll
+    for (int e = 0; e < EPL; ++e) {
+      const int j = lane * EPL + e;
+      b[e] = f2bf((r < R && j < D) ? (float)x[(size_t)r * D + j] : 0.f);
+    }
   }
   typename BfVec<EPL>::type o;
 #pragma unroll
-  for (int e = 0; e < EPL; ++e) o[e] = f2bf(NORM ? v[e] * iv : v[e]);
+  for (int e = 0; e < EPL; ++e) o[e] = b[e];
   *(typename BfVec<EPL>::type*)(y + (size_t)r * DP + lane * EPL) = o;
 }
 
@@ -164,17 +141,8 @@ __global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) knn_rows_kernel(const K
   const int tid = threadIdx.x, lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const uint32_t q = lane >> 4, l15 = lane & 15;
-  // XCD-aware (query block, split): workgroups are dispatched round-robin over the 8 XCDs, so the ones
-  // sharing an XCD (and its L2) take the SAME gallery splits for all query blocks
-  int rb = blockIdx.x, split = blockIdx.y;
-  {
-    const int RB = gridDim.x, S = gridDim.y, L = blockIdx.x + blockIdx.y * RB;
-    if ((S & 7) == 0) {
-      const int xcd = L & 7, idx = L >> 3;
-      split = xcd * (S >> 3) + idx / RB;
-      rb = idx % RB;
-    }
-  }
+  int rb, split;  // (query block, gallery split)
+  xcd_row_split(rb, split);
   const int row = rb * 64 + w * 16 + (int)l15;
   bf16x8 xf[KS];
 #pragma unroll
@@ -190,14 +158,12 @@ __global__ void __launch_bounds__(256, KS == 16 ? 1 : 2) knn_rows_kernel(const K
 
   const int ntiles = p.Ngp / kKnnTile;
   const int t0 = split * p.tps, t1 = min(ntiles, t0 + p.tps);
-  if (t0 < t1) dma_rm<DP>(smem, p.gn, t0 * kKnnTile, w, lane);
+  if (t0 < t1) dma_rm<DP, kKnnTile>(smem, p.gn, t0 * kKnnTile, w, lane);
   for (int tile = t0; tile < t1; ++tile) {
     const int c0 = tile * kKnnTile, b = (tile - t0) & 1;
     const char* Gt = smem + b * BUF;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // this tile landed for every wave; the other buffer's reads are done
-    asm volatile("" ::: "memory");
-    if (tile + 1 < t1) dma_rm<DP>(smem + (b ^ 1) * BUF, p.gn, (tile + 1) * kKnnTile, w, lane);
+    tile_landed();  // this tile landed for every wave; the other buffer's reads are done
+    if (tile + 1 < t1) dma_rm<DP, kKnnTile>(smem + (b ^ 1) * BUF, p.gn, (tile + 1) * kKnnTile, w, lane);
     f32x4 acc[NJ];
 #pragma unroll
     for (int j = 0; j < NJ; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -307,13 +273,9 @@ __global__ void __launch_bounds__(256) knn_merge_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------
-namespace {
-bool knn_dp_ok(int Dp) { return Dp == 128 || Dp == 256 || Dp == 512; }
-}  // namespace
-
 bool launch_knn_prep(const void* x, bool is_bf16, int R, int D, int Rp, int Dp, bool normalize, bf16* y, float eps,
                      hipStream_t st) {
-  if (Rp % 64 || Rp < R || D > Dp || !knn_dp_ok(Dp)) return false;
+  if (Rp % 64 || Rp < R || D > Dp || !score_dp_ok(Dp)) return false;
 #define KNN_PREP(T_, DP_)                                                                                        \
   if (normalize)                                                                                                 \
     hipLaunchKernelGGL((knn_prep_kernel<T_, DP_, true>), dim3(Rp / 4), dim3(256), 0, st, (const T_*)x, R, D, Rp, \
@@ -335,18 +297,15 @@ int knn_kmax(int k) { return k < 1 || k > 8 ? 0 : k == 1 ? 1 : k <= 4 ? 4 : 8; }
 int knn_splits(int Nqp, int Ngp) {
   // ~ 1024 workgroups (4 per CU), at most 64 splits (the merge kernel's lanes); multiples of 8 take
   // the XCD-aware mapping
-  const int blocks = std::max(1, Nqp / 64), ntiles = std::max(1, Ngp / kKnnTile);
-  int s = (1024 + blocks - 1) / blocks;
-  s = std::max(1, std::min(s, std::min(ntiles, 64)));
-  return s >= 8 ? s / 8 * 8 : s;
+  return score_splits(Nqp / 64, Ngp / kKnnTile, 1024, 64);
 }
 
 bool launch_knn_topk(const bf16* qn, const bf16* gn, int Nq, int Nqp, int Ng, int Ngp, int Dp, int k, int S,
                      const int* exclude, const int64_t* q_labels, const int64_t* g_labels, float* pval, int* pidx,
                      float* val, int* idx, int* first_hit, hipStream_t st) {
   const int kmax = knn_kmax(k);
-  if (Nqp % 64 || Ngp % kKnnTile || Nq < 1 || Nq > Nqp || Ng < 1 || Ng > Ngp || !knn_dp_ok(Dp) || kmax == 0 || S < 1 ||
-      S > 64)
+  if (Nqp % 64 || Ngp % kKnnTile || Nq < 1 || Nq > Nqp || Ng < 1 || Ng > Ngp || !score_dp_ok(Dp) || kmax == 0 ||
+      S < 1 || S > 64)
     return false;
   if ((q_labels == nullptr) != (g_labels == nullptr) || (q_labels != nullptr && first_hit == nullptr)) return false;
   KnnParams p{};
@@ -357,8 +316,7 @@ bool launch_knn_topk(const bf16* qn, const bf16* gn, int Nq, int Nqp, int Ng, in
   const dim3 grid(Nqp / 64, S);
 #define KNN_ROWS(KS_, KM_)                                                                                      \
   {                                                                                                             \
-    (void)hipFuncSetAttribute((const void*)knn_rows_kernel<KS_, KM_>, hipFuncAttributeMaxDynamicSharedMemorySize, \
-                              (int)lds);                                                                        \
+    score_set_lds((const void*)knn_rows_kernel<KS_, KM_>, lds);                                                 \
     hipLaunchKernelGGL((knn_rows_kernel<KS_, KM_>), grid, dim3(256), lds, st, p);                               \
   }
 #define KNN_ROWS_K(KS_) \

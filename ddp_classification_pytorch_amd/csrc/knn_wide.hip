@@ -1,8 +1,9 @@
 // Fused cosine / dot-product top-k for 1 <= k <= 256 and the weighted kNN label vote on top of it.
-// Same contract as knn.hip (operands from knn_prep_kernel, order = score descending then gallery index
-// ascending, never a candidate: padding rows, exclude[r], NaN scores; tail (-inf, -1); the bits do not
-// depend on the number of gallery splits), another selection: a register list costs KMAX selects per
-// insertion and stops at 8, so here every query row of the workgroup owns a CANDIDATE POOL in LDS.
+// The streamed tile is score_tile.cuh's.  Same contract as knn.hip (operands from knn_prep_kernel,
+// order = score descending then gallery index ascending, never a candidate: padding rows, exclude[r],
+// NaN scores; tail (-inf, -1); the bits do not depend on the number of gallery splits), another
+// selection: a register list costs KMAX selects per insertion and stops at 8, so here every query row
+// of the workgroup owns a CANDIDATE POOL in LDS.
 //
 //   select  knn_pool_rows_kernel  grid (query blocks of 32, S gallery splits), XCD-aware for S % 8 == 0.
 //                                 4 waves = 2 query groups of 16 rows x 2 halves of the T-row gallery tile;
@@ -53,8 +54,8 @@
 //     16   256  32  112   64 KB    92 KB    156.3 KB    130 + 4            0
 //
 // Scratch is 0 in every instantiation.
-#include "common.cuh"
 #include "launchers.h"
+#include "score_tile.cuh"
 
 namespace dcp {
 
@@ -70,23 +71,6 @@ struct KnnPoolParams {
   int* pidx;           // [S][Nqp][KCAP]
   int Nq, Nqp, Ng, Ngp, tps;
 };
-
-// byte offset of 16-byte chunk c of row r in a row-major [T][Dp] bf16 tile, XOR-swizzled as in knn.hip
-__device__ __forceinline__ uint32_t rm_off(uint32_t r, uint32_t c, uint32_t Dp) {
-  return r * Dp * 2u + ((c ^ (r & 15u)) << 4);
-}
-// LDS-DMA staging of a T-row tile by 4 waves (untracked: vmcnt(0) + barrier before it is read)
-template <int DP, int T>
-__device__ __forceinline__ void dma_tile(char* L, const bf16* g, int r0, int w, int lane) {
-  constexpr int CPR = DP / 8, RPB = 64 / CPR, NI = T / RPB / 4;  // rows per 1 KB block; blocks per wave
-#pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int blk = w * NI + i;
-    const int r = blk * RPB + lane / CPR, pos = lane % CPR;
-    const int c = pos ^ (r & 15);
-    dma16(g + (size_t)(r0 + r) * DP + c * 8, L + blk * 1024);
-  }
-}
 
 // (score, index) as one key: a larger key is earlier in the order (score descending, index ascending)
 constexpr uint64_t kPoolFiller = 0x007FFFFF00000000ull;  // (-inf, -1): below every key that can enter
@@ -162,16 +146,8 @@ __global__ void __launch_bounds__(256, 1) knn_pool_rows_kernel(const KnnPoolPara
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int qg = w & 1, half = w >> 1;  // query rows 16 qg .., gallery rows half T / 2 .. of a tile
   const uint32_t q = lane >> 4, l15 = lane & 15;
-  // XCD-aware (query block, split) as in knn_rows_kernel
-  int rb = blockIdx.x, split = blockIdx.y;
-  {
-    const int RB = gridDim.x, S = gridDim.y, L = blockIdx.x + blockIdx.y * RB;
-    if ((S & 7) == 0) {
-      const int xcd = L & 7, idx = L >> 3;
-      split = xcd * (S >> 3) + idx / RB;
-      rb = idx % RB;
-    }
-  }
+  int rb, split;  // (query block, gallery split)
+  xcd_row_split(rb, split);
   const int lrow = qg * 16 + (int)l15, row = rb * kPoolRows + lrow;
   bf16x8 xf[KS];
 #pragma unroll
@@ -187,14 +163,12 @@ __global__ void __launch_bounds__(256, 1) knn_pool_rows_kernel(const KnnPoolPara
 
   const int ntiles = p.Ngp / T;
   const int t0 = split * p.tps, t1 = min(ntiles, t0 + p.tps);
-  if (t0 < t1) dma_tile<DP, T>(smem, p.gn, t0 * T, w, lane);
+  if (t0 < t1) dma_rm<DP, T>(smem, p.gn, t0 * T, w, lane);
   for (int tile = t0; tile < t1; ++tile) {
     const int c0 = tile * T, b = (tile - t0) & 1;
     const char* Gt = smem + b * BUF;
-    asm volatile("s_waitcnt vmcnt(0)\n\ts_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // A: this tile landed; the last tile's reads and appends are complete
-    asm volatile("" ::: "memory");
-    if (tile + 1 < t1) dma_tile<DP, T>(smem + (b ^ 1) * BUF, p.gn, (tile + 1) * T, w, lane);
+    tile_landed();  // A: this tile landed; the last tile's reads and appends are complete
+    if (tile + 1 < t1) dma_rm<DP, T>(smem + (b ^ 1) * BUF, p.gn, (tile + 1) * T, w, lane);
     // Nobody appends between A and B, so the counters are stable; a wave looks at its own 8 rows only
     // and B is unconditional: no barrier depends on what a wave read.
     // INVARIANT: after B every count is <= P - T, a tile appends at most T keys to a row, so a slot
@@ -350,16 +324,13 @@ int knn_wide_splits(int Nqp, int Ngp) {
   // ~ 1024 workgroups of 32 query rows, at most 64 splits (the merge kernel's lanes), multiples of 8 for
   // the XCD-aware mapping: S blocks < 1024 + blocks, so the partials hold fewer than (32768 + Nqp) KCAP
   // (score, index) pairs
-  const int blocks = std::max(1, Nqp / kPoolRows), ntiles = std::max(1, Ngp / 64);
-  int s = (1024 + blocks - 1) / blocks;
-  s = std::max(1, std::min(s, std::min(ntiles, 64)));
-  return s >= 8 ? s / 8 * 8 : s;
+  return score_splits(Nqp / kPoolRows, Ngp / 64, 1024, 64);
 }
 
 bool launch_knn_topk_wide(const bf16* qn, const bf16* gn, int Nq, int Nqp, int Ng, int Ngp, int Dp, int k, int S,
                           const int* exclude, float* pval, int* pidx, float* val, int* idx, hipStream_t st) {
   const int kcap = knn_wide_kcap(k);
-  if (Nqp % 64 || Ngp % 64 || Nq < 1 || Nq > Nqp || Ng < 1 || Ng > Ngp || (Dp != 128 && Dp != 256 && Dp != 512) ||
+  if (Nqp % 64 || Ngp % 64 || Nq < 1 || Nq > Nqp || Ng < 1 || Ng > Ngp || !score_dp_ok(Dp) ||
       kcap == 0 || S < 1 || S > 64)
     return false;
   const int T = knn_wide_tile(Dp, kcap), NEW = kcap == 256 ? 112 : 64;

@@ -478,6 +478,11 @@ bool launch_arcface_fused_dw(const bf16* xn, const bf16* xnT, const bf16* wn, co
                              int C, int Cp, int Dp, int D, float s, const float* lab, const float* lse,
                              const float* gout, float scale, const float* inv_w, float* part, float* info,
                              float* dw, hipStream_t st);
+// The finalize kernel both heads share (arcface.hip): the forward split partials part [S][Bp][4] ->
+// loss [B], rank [B] (or null), lse [Bp].  label64: a label is valid by all its 64 bits (the sub-centre
+// head's rule); false: by its low 32 bits read as int (the plain head's).
+void launch_arc_fwd_finalize(const float* part, int S, int B, int Bp, int C, const int64_t* labels, const float* lab,
+                             float* loss, int* rank, float* lse, bool label64, hipStream_t st);
 // Fused Sub-center ArcFace head (arcface_sub.hip): K in {2, 3, 4} centres per class, Dp in {128, 256}.
 // The centre operands wn [Wp][Dp], wnT [Dp][Wp], inv_w [Wp] use the planar row order of that file,
 // Wp = arcface_sub_rows(C, K); xn / xnT / inv_x come from launch_arcface_l2norm_t.  The partial buffers

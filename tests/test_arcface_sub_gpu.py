@@ -100,6 +100,29 @@ def test_sub_head_lattice(lattice_cases, B, C, K, D, easy):
     assert ex <= SUB_DX_TOL and ew <= SUB_DW_TOL, (ex, ew)
 
 
+def test_sub_head_label_past_int32_is_invalid(lattice_cases):
+    """A label whose low 32 bits name a class (2^32 + 5) is invalid to every kernel of the head, the
+    shared finalize kernel included: the same outputs as for -1, a zero loss and a zero dX row."""
+    ops = _ext.hip_ops()
+    B, C, K, D = LATTICE[0]
+    x, W, lab = lattice_cases[B, C, K, D][:3]
+    Dp, Bp = Fn.arcface_sub_check(K, D), Fn.round_up(B, 64)
+    go = torch.tensor([GO], device=DEV)
+    xn, xnT, inv_x = ops.arcface_l2norm_t(x.to(DEV), Bp, Dp, 1e-12)
+    wn, wnT, inv_w = ops.arcface_sub_l2norm_t(W.to(DEV), Dp, 1e-12)
+    assert lab[1].item() == -1
+    outs = []
+    for bad in (-1, 2 ** 32 + 5):
+        labd = lab.clone()
+        labd[1] = bad
+        labd = labd.to(DEV)
+        loss, rank, lse, labt, sub = ops.arcface_sub_fwd(xn, wn, labd, B, C, K, S, M, True)
+        dx = ops.arcface_sub_dx(xn, wn, wnT, labd, lse, labt, sub, go, 1.0 / B, inv_x, B, C, K, D, S, False)
+        outs.append((loss, rank, lse, labt, sub, dx))
+    assert outs[1][0][1].item() == 0 and outs[1][5][1].abs().max().item() == 0
+    assert all(torch.equal(a, b) for a, b in zip(*outs))
+
+
 def _relerr(a, b):
     a, b = a.float().cpu(), b.float().cpu()
     return ((a - b).norm() / (b.norm() + 1e-12)).item()

@@ -64,6 +64,25 @@ def test_same_bits_for_any_split_count():
         assert all(torch.equal(a, b) for a, b in zip(o, outs[0]))
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("D", [100, 200, 300])
+def test_operand_bits_equal_arcface_operands(D, dtype):
+    """knn_prep with normalize=True and the ArcFace operand kernel normalise a row through the same
+    helper (csrc/score_tile.cuh: norm_row): the same bits, and zero padding in both."""
+    from ddp_classification_pytorch_amd import _ext
+
+    torch.manual_seed(3)
+    x = torch.randn(70, D, device=DEV).to(dtype)
+    Dp = Fn.arcface_fused_dp(D)
+    assert Dp == {100: 128, 200: 256, 300: 512}[D]
+    kn = Fn.knn_operand(x)
+    an = _ext.hip_ops().arcface_l2norm_t(x, 128, Dp, 1e-12)[0]
+    assert kn.shape == (128, Dp) and an.shape == (128, Dp)
+    assert torch.equal(kn[:70], an[:70]) and kn[:70, :D].any()
+    for t in (kn, an):
+        assert not t[70:].any() and not t[:, D:].any()
+
+
 @pytest.mark.parametrize("Nq,Ng,D,k", [(130, 700, 256, 8), (70, 300, 512, 4)])
 def test_random_normalised_within_fp32_bound(Nq, Ng, D, k):
     """Against fp64 on the SAME bf16 operands (the preparation kernel's output).  Products of two bf16
