@@ -40,7 +40,7 @@ def run(args):
 
     refuse_knn(args, "baseline")
     rt = setup(args)
-    train_data, val_data, _, _ = build_data(args, rt)
+    train_data, val_data, train_set, _ = build_data(args, rt)
     model = build_classifier(args).to(rt.device)
     net = wrap_ddp(model, rt.local_rank, syncbn=args.syncbn and (rt.world > 1 or args.force_ddp), bucket_cap_mb=args.bucket_cap_mb,
                    first_bucket_mb=args.first_bucket_mb, force=args.force_ddp)
@@ -50,13 +50,30 @@ def run(args):
     sched = StepLR(opt, step_size=args.step_size, gamma=args.gamma)
     C = args.num_classes
     mixed = getattr(train_data, "mix", None) is not None
+    # --loss gce | sce | elr (csrc/loss_robust.hip; config.check_loss refused every combination it does not
+    # cover).  elr: the loaders append the dataset index, and the fp32 [N_train, C] target table lives on the
+    # device, updated inside the (captured) step and carried by the checkpoints
+    loss_name, loss_state = getattr(args, "loss", "ce"), {}
+    if loss_name == "elr":
+        n_train = len(train_set) if train_set is not None else train_data.num_samples
+        loss_state["elr_table"] = torch.zeros(n_train, C, dtype=torch.float32, device=rt.device)
+
+    def robust_plan(batch):
+        if loss_name == "gce":
+            return ("gce", args.gce_q)
+        if loss_name == "sce":
+            return ("sce", args.sce_alpha, args.sce_beta)
+        if loss_name == "elr":
+            return ("elr", args.elr_lambda, args.elr_beta, loss_state["elr_table"], batch[-1])
+        return None
 
     def fwd_train(batch):
         x, y = batch[0], batch[1]
         # a Mixup / CutMix loader yields (x, labels, partner, wlab): the two-label loss (the rank it
         # returns, and so the training top-1 / top-3, is against the row's own label)
         mix = (batch[2], batch[3]) if mixed else None
-        return Fn.cross_entropy(net(x), y, C, smoothing=args.label_smoothing, return_rank=True, mix=mix)
+        return Fn.cross_entropy(net(x), y, C, smoothing=args.label_smoothing, return_rank=True, mix=mix,
+                                robust=robust_plan(batch))
 
     def fwd_eval(batch):
         x, y = batch[0], batch[1]
@@ -64,5 +81,5 @@ def run(args):
 
     models = {"model": model}
     loop = ClassificationLoop(args, rt, models, opt, sched, train_data, val_data, fwd_train, fwd_eval,
-                              train_modules=[net], ema=build_ema(args, models, opt))
+                              train_modules=[net], ema=build_ema(args, models, opt), loss_state=loss_state)
     return loop.run()

@@ -132,6 +132,15 @@ def build_parser() -> argparse.ArgumentParser:
     a("--lrSchedule", "--milestones", dest="milestones", type=int, nargs="+", default=None)
     a("--warmup-iters", "--warmUpIter", dest="warmup_iters", type=int, default=0)
     a("--label-smoothing", type=float, default=0.0)
+    # noise-robust losses on the device (csrc/loss_robust.hip; the baseline workload only)
+    a("--loss", default="ce", choices=["ce", "gce", "sce", "elr"],
+      help="ce: softmax cross-entropy; gce: generalised CE (1 - p^q) / q; sce: symmetric CE; elr: early-learning "
+           "regularisation with a moving-average target per training sample (one process only)")
+    a("--gce-q", dest="gce_q", type=float, default=0.7, help="GCE: q in (0, 1]")
+    a("--sce-alpha", dest="sce_alpha", type=float, default=1.0, help="SCE: weight of the cross-entropy term")
+    a("--sce-beta", dest="sce_beta", type=float, default=1.0, help="SCE: weight of the reverse cross-entropy term")
+    a("--elr-lambda", dest="elr_lambda", type=float, default=3.0, help="ELR: weight of the regulariser")
+    a("--elr-beta", dest="elr_beta", type=float, default=0.7, help="ELR: momentum of the per-sample target")
     # Mixup / CutMix on the device (data/mix.py; the baseline workload only)
     a("--mixup-alpha", dest="mixup_alpha", type=float, default=0.0,
       help="Mixup: lam ~ Beta(alpha, alpha) blends each image and label with its partner's (0 = off)")
@@ -263,7 +272,31 @@ def resolve(args: argparse.Namespace) -> argparse.Namespace:
     if args.nested > 0 and args.dropout > 0:
         raise ValueError("nested dropout and standard dropout are mutually exclusive (NESTED/train.py:489-490)")
     check_randaug(args)
+    check_loss(args)
     return args
+
+
+def check_loss(args):
+    """--loss gce|sce|elr at start-up: a workload other than baseline, a mix flag, label smoothing, a
+    hyper-parameter out of range or elr on several ranks is an error, never silently ignored."""
+    loss = getattr(args, "loss", "ce") or "ce"
+    if loss == "ce":
+        return
+    if args.workload != "baseline":
+        raise ValueError(f"--loss {loss}: the noise-robust losses are wired for --workload baseline only, not "
+                         f"{args.workload}")
+    if mix_enabled(args):
+        raise ValueError(f"--loss {loss} takes one hard label per image: not with --mixup-alpha / --cutmix-alpha")
+    if float(getattr(args, "label_smoothing", 0.0) or 0.0) > 0:
+        raise ValueError(f"--loss {loss} takes one hard label per image: not with --label-smoothing")
+    if loss == "gce" and not 0.0 < float(args.gce_q) <= 1.0:
+        raise ValueError(f"--gce-q covers 0 < q <= 1, got {args.gce_q}")
+    if loss == "elr":
+        if not 0.0 <= float(args.elr_beta) < 1.0:
+            raise ValueError(f"--elr-beta covers 0 <= beta < 1, got {args.elr_beta}")
+        if int(args.world_size) > 1:
+            raise ValueError("--loss elr runs in one process: a sample changes rank between epochs and the target "
+                             "table is not synchronised between ranks yet")
 
 
 def mix_enabled(args) -> bool:

@@ -1963,6 +1963,61 @@ Tensor xent_mix_bwd(const Tensor& logits, const Tensor& labels, const Tensor& pa
   return d;
 }
 
+// noise-robust losses (loss_robust.hip).  mode 0 gce (a0 = q), 1 sce (a0 = alpha, a1 = beta), 2 elr (a0 = lam,
+// a1 = mom): elr takes the target table fp32 [N, C] (updated in place by the forward) and idx int64 [B]
+static int64_t check_robust(const Tensor& logits, const Tensor& labels, int64_t C, int64_t mode,
+                            const c10::optional<Tensor>& table, const c10::optional<Tensor>& idx) {
+  CHECK_DEV(logits);
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "logits rows must be contiguous");
+  TORCH_CHECK(logits.scalar_type() == at::kBFloat16 || logits.scalar_type() == at::kFloat, "logits bf16 or fp32");
+  const int64_t B = logits.size(0);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda() && labels.is_contiguous() && labels.numel() == B,
+              "labels int64 [B] on GPU");
+  TORCH_CHECK(C >= 1 && C <= logits.size(1) && C <= logits.stride(0), "xent_robust shapes");
+  TORCH_CHECK(mode >= 0 && mode <= 2, "xent_robust mode: 0 gce, 1 sce, 2 elr");
+  if (mode != 2) return 0;
+  TORCH_CHECK(table.has_value() && idx.has_value(), "xent_robust elr needs table and idx");
+  const Tensor &t = *table, &i = *idx;
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.dim() == 2 && t.is_contiguous() && t.size(1) == C,
+              "table fp32 [N, C] contiguous on GPU");
+  TORCH_CHECK(i.is_cuda() && i.scalar_type() == at::kLong && i.is_contiguous() && i.numel() == B,
+              "idx int64 [B] on GPU");
+  return t.size(0);
+}
+
+// -> (loss_rows, rank, rec fp64 [B, 4] = (lse, c, s, s_m))
+std::tuple<Tensor, Tensor, Tensor> xent_robust_fwd(const Tensor& logits, const Tensor& labels, int64_t C, int64_t mode,
+                                                   double a0, double a1, const c10::optional<Tensor>& table,
+                                                   const c10::optional<Tensor>& idx) {
+  const int64_t N = check_robust(logits, labels, C, mode, table, idx);
+  TORCH_CHECK(mode != 0 || (a0 > 0 && a0 <= 1), "xent_robust gce covers 0 < q <= 1");
+  const int B = logits.size(0), ld = logits.stride(0);
+  auto loss = at::empty({B}, f32_like(logits));
+  auto rank = at::empty({B}, logits.options().dtype(at::kInt));
+  auto rec = at::empty({B, 4}, logits.options().dtype(at::kDouble));
+  dcp::launch_xent_robust_fwd(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, B, ld, C,
+                              labels.data_ptr<int64_t>(), (int)mode, (float)a0, (float)a1,
+                              N ? table->data_ptr<float>() : nullptr, N ? idx->data_ptr<int64_t>() : nullptr, N,
+                              loss.data_ptr<float>(), rank.data_ptr<int>(), rec.data_ptr<double>(), cur_stream());
+  return {loss, rank, rec};
+}
+
+Tensor xent_robust_bwd(const Tensor& logits, const Tensor& labels, int64_t C, const Tensor& rec, int64_t mode,
+                       double lam, const c10::optional<Tensor>& table, const c10::optional<Tensor>& idx,
+                       const Tensor& grad_out, double scale, bool out_bf16) {
+  const int64_t N = check_robust(logits, labels, C, mode, table, idx);
+  const int B = logits.size(0), ld = logits.stride(0), ldo = logits.size(1);
+  TORCH_CHECK(rec.is_cuda() && rec.scalar_type() == at::kDouble && rec.is_contiguous() && rec.numel() == 4 * (int64_t)B,
+              "rec fp64 [B, 4] on GPU");
+  auto d = at::empty({B, ldo}, logits.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+  auto g = grad_out.to(at::kFloat).contiguous();
+  dcp::launch_xent_robust_bwd(logits.data_ptr(), logits.scalar_type() == at::kBFloat16, B, ld, C,
+                              labels.data_ptr<int64_t>(), rec.data_ptr<double>(), (int)mode, (float)lam,
+                              N ? table->data_ptr<float>() : nullptr, N ? idx->data_ptr<int64_t>() : nullptr, N,
+                              g.data_ptr<float>(), (float)scale, d.data_ptr(), ldo, out_bf16, cur_stream());
+  return d;
+}
+
 Tensor log_softmax_fwd(const Tensor& x, int64_t C) {
   CHECK_DEV(x);
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, "rows must be contiguous");
@@ -2848,6 +2903,12 @@ TORCH_LIBRARY(dcp, m) {
   m.def("xent_mix_bwd(Tensor logits, Tensor labels, Tensor partner, Tensor wlab, int C, Tensor grad_out, float scale, "
         "float smoothing, bool out_bf16) -> Tensor",
         &xent_mix_bwd);
+  m.def("xent_robust_fwd(Tensor logits, Tensor labels, int C, int mode, float a0, float a1, Tensor(a!)? table, "
+        "Tensor? idx) -> (Tensor, Tensor, Tensor)",
+        &xent_robust_fwd);
+  m.def("xent_robust_bwd(Tensor logits, Tensor labels, int C, Tensor rec, int mode, float lam, Tensor? table, "
+        "Tensor? idx, Tensor grad_out, float scale, bool out_bf16) -> Tensor",
+        &xent_robust_bwd);
   m.def("log_softmax_fwd(Tensor x, int C) -> Tensor", &log_softmax_fwd);
   m.def("log_softmax_bwd(Tensor y, Tensor dy, int ldo, bool out_bf16) -> Tensor", &log_softmax_bwd);
   m.def("s2d_weight(Tensor w7, Tensor(a!) w16) -> ()", &s2d_weight);

@@ -275,6 +275,14 @@ void launch_xent_mix_fwd(const void* logits, bool is_bf16, int B, int ld, int C,
 void launch_xent_mix_bwd(const void* logits, bool in_bf16, int B, int ld, int C, const int64_t* labels,
                          const int* partner, const float* wlab, const float* grad_out, float scale, float smoothing,
                          void* dlogits, int ldo, bool out_bf16, hipStream_t s);
+// noise-robust losses (loss_robust.hip): mode 0 gce (a0 = q), 1 sce (a0 = alpha, a1 = beta), 2 elr (a0 = lam,
+// a1 = mom; table fp32 [N][C] updated in place at the rows idx[b]).  rec fp64 [B][4] = (lse, c, s, s_m).
+void launch_xent_robust_fwd(const void* logits, bool is_bf16, int B, int ld, int C, const int64_t* labels, int mode,
+                            float a0, float a1, float* table, const int64_t* idx, int64_t N, float* loss, int* rank,
+                            double* rec, hipStream_t s);
+void launch_xent_robust_bwd(const void* logits, bool in_bf16, int B, int ld, int C, const int64_t* labels,
+                            const double* rec, int mode, float lam, const float* table, const int64_t* idx, int64_t N,
+                            const float* grad_out, float scale, void* dlogits, int ldo, bool out_bf16, hipStream_t s);
 void launch_log_softmax_fwd(const void* x, bool is_bf16, int B, int ld, int C, float* y, hipStream_t s);
 void launch_log_softmax_bwd(const float* y, const float* dy, int B, int C, int ldo, void* dx, bool out_bf16,
                             hipStream_t s);

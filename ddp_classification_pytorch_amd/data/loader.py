@@ -117,6 +117,7 @@ class SyntheticLoader:
         self.mix, self.size = mix, size  # mix: a MixSampler -> (x, labels, partner, wlab[, index])
         self.steps, self.cpad, self.return_index, self.batch_size = steps, cpad, return_index, batch_size
         self.s2d = Fn.s2d_for(s2d, size, size)
+        self.num_samples = pool * batch_size  # the indices return_index yields are below this
         g = torch.Generator(device="cpu")
         g.manual_seed(seed)
         self.imgs = [torch.randint(0, 256, (batch_size, size, size, 3), dtype=torch.uint8, generator=g).to(self.device)

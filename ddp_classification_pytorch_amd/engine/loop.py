@@ -164,8 +164,11 @@ class ClassificationLoop:
 
     def __init__(self, args, rt, models: dict, optimizer, scheduler, train_data, val_data, forward_train,
                  forward_eval, post_backward=None, logger: MetricsLogger = None, scheduler_before_epoch=False,
-                 train_modules=None, ema=None, embed_eval=None):
+                 train_modules=None, ema=None, embed_eval=None, loss_state=None):
         self.args, self.rt = args, rt
+        # device tensors the loss updates in place (--loss elr: the per-sample target table); they ride the
+        # checkpoints like the EMA state
+        self.loss_state = loss_state or {}
         self.models, self.optimizer, self.scheduler = models, optimizer, scheduler
         self.train_data, self.val_data = train_data, val_data
         self.forward_train, self.forward_eval = forward_train, forward_eval
@@ -217,6 +220,12 @@ class ClassificationLoop:
             if extra.get("ema") is None:
                 raise RuntimeError(f"--model-ema: {path} carries no weight EMA (it was written without the flag)")
             self.ema.load_state_dict(extra["ema"])
+        for name, t in self.loss_state.items():
+            saved = (extra.get("loss_state") or {}).get(name)
+            if saved is None or tuple(saved.shape) != tuple(t.shape):
+                raise RuntimeError(f"--loss {getattr(self.args, 'loss', 'ce')}: {path} carries no {name} of shape "
+                                   f"{tuple(t.shape)} (it was written without the flag or for another dataset)")
+            t.copy_(saved)
         self.logger.line(f"resumed from {path}: epoch {self.start_epoch}, step {self.global_step}")
 
     def save(self, epoch, val_top1):
@@ -225,6 +234,8 @@ class ClassificationLoop:
                   config={k: v for k, v in vars(self.args).items() if isinstance(v, (int, float, str, bool, list))})
         if self.ema is not None:
             kw["ema"] = self.ema.state_dict()
+        if self.loss_state:
+            kw["loss_state"] = {k: v.detach().cpu() for k, v in self.loss_state.items()}
         sched = {"sched": self.scheduler} if self.scheduler is not None else None
         save_checkpoint(self._ckpt("last.pth"), self.models, {"opt": self.optimizer}, sched, **kw)
         if val_top1 > self.best:

@@ -59,6 +59,12 @@ def setup(args) -> Runtime:
     return Runtime(rank, local, world, device)
 
 
+def wants_index(args) -> bool:
+    """The loaders append the dataset index to every batch: PLC relabels its dataset, ELR keeps a target
+    per training sample."""
+    return args.workload == "plc" or getattr(args, "loss", "ce") == "elr"
+
+
 def _datasets(args):
     tr_t = build_transform(args.transform, True, args.image_size)
     va_t = build_transform(args.transform, False, args.image_size)
@@ -67,9 +73,9 @@ def _datasets(args):
         size = args.image_size if args.transform != "baseline" or args.image_size != 224 else 224
         learn = getattr(args, "synthetic_learnable", False)
         tr = SyntheticImages(n_tr, size=size, num_classes=args.num_classes, seed=args.seed,
-                             return_index=args.workload == "plc", learnable=learn)
+                             return_index=wants_index(args), learnable=learn)
         va = SyntheticImages(n_va, size=size, num_classes=args.num_classes, seed=args.seed + 1,
-                             return_index=args.workload == "plc", learnable=learn)
+                             return_index=wants_index(args), learnable=learn)
         return tr, va
     if args.data == "shards":
         from ..data.shards import ShardDataset
@@ -157,7 +163,7 @@ def _shard_loaders(args, rt, tr, va, tr_s, va_s, mean, std, cpad, s2d, drop_last
     except ValueError:
         return None
     _check_randaug_size(args, tr_size)
-    idx = args.workload == "plc"
+    idx = wants_index(args)
     kw = dict(device=rt.device, threads=args.loader_threads, seed=args.seed, mean=mean, std=std, cpad=cpad,
               return_index=idx, resample=resample)
     tr_l = ShardLoader(tr.path, args.batchsize, tr_s, tr_aug, tr_size, drop_last=drop_last_train,
@@ -181,7 +187,7 @@ def _device_synthetic(args, rt: Runtime):
               s2d=s2d)
     B = args.batchsize
     tr = SyntheticLoader(B, max(1, args.synthetic_train_size // B), seed=args.seed + 17 * rt.rank,
-                         mix=_mix_sampler(args, rt), **kw)
+                         mix=_mix_sampler(args, rt), return_index=wants_index(args), **kw)
     va = SyntheticLoader(B, max(1, args.synthetic_val_size // B), seed=args.seed + 17 * rt.rank + 7, **kw)
     return tr, va, None, None
 
@@ -190,7 +196,7 @@ def build_data(args, rt: Runtime, drop_last_train=False):
     if args.data == "synthetic-device":
         return _device_synthetic(args, rt)
     tr, va = _datasets(args)
-    if args.workload == "plc" and args.data != "synthetic" and not isinstance(tr, ListDataset):
+    if wants_index(args) and args.data != "synthetic" and not isinstance(tr, ListDataset):
         tr, va = WithIndex(tr), WithIndex(va)
     mean, std = norm_stats(args.dataset if "CIFAR" in args.dataset.upper() else "imagenet")
     cpad = 3 if str(args.model).startswith("tresnet") else 8

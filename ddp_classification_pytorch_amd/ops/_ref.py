@@ -849,6 +849,69 @@ def xent_mix_bwd(logits, labels, partner, wlab, C, grad_out, scale, smoothing, o
     return d.to(torch.bfloat16 if out_bf16 else torch.float32)
 
 
+_ELR_LO, _ELR_HI, _SCE_A = 1e-4, 1 - 1e-4, -math.log(1e-4)
+
+
+def _robust_rows(logits, labels, C, mode, table, idx):
+    x = _f(logits)[:, :C]
+    a = labels.view(-1).long()
+    valid = (a >= 0) & (a < C)
+    i = None
+    if mode == 2:
+        i = idx.view(-1).long()
+        valid = valid & (i >= 0) & (i < table.shape[0])
+    lse = torch.logsumexp(x, 1)
+    xa = torch.where((a >= 0) & (a < C), x.gather(1, a.clamp(0, C - 1).view(-1, 1)).squeeze(1), torch.zeros_like(lse))
+    return x, a, i, valid, lse, xa
+
+
+def xent_robust_fwd(logits, labels, C, mode, a0, a1, table, idx):
+    """Noise-robust losses (csrc/loss_robust.hip): mode 0 gce (a0 = q), 1 sce (a0 = alpha, a1 = beta),
+    2 elr (a0 = lam, a1 = mom; ``table`` fp32 [N, C] is updated in place at the rows ``idx``, which must be
+    distinct).  -> (loss rows, rank, rec [B, 4] = (lse, c, s, s_m)); an invalid row has loss 0."""
+    x, a, i, valid, lse, xa = _robust_rows(logits, labels, C, mode, table, idx)
+    ce = lse - xa
+    s = sm = torch.zeros_like(lse)
+    if mode == 0:
+        c = torch.exp(-a0 * ce)
+        loss = (1 - c) / a0
+    elif mode == 1:
+        pa = torch.exp(-ce)
+        c = a0 + a1 * _SCE_A * pa
+        loss = a0 * ce + a1 * _SCE_A * (1 - pa)
+    else:
+        p = torch.exp(x - lse.unsqueeze(1))
+        pc = p.clamp(_ELR_LO, _ELR_HI)
+        rows = i[valid]
+        t = a1 * table[rows] + (1 - a1) * pc[valid] / pc[valid].sum(1, keepdim=True)
+        table[rows] = t
+        inside = ((p > _ELR_LO) & (p < _ELR_HI)).float()
+        s, sm = torch.zeros_like(lse), torch.zeros_like(lse)
+        s[valid] = (pc[valid] * t).sum(1)
+        sm[valid] = (inside[valid] * p[valid] * t).sum(1)
+        c = torch.ones_like(lse)
+        loss = ce + a0 * torch.log1p(-s)
+    rank = (x > xa.unsqueeze(1)).sum(1).int()
+    return torch.where(valid, loss, torch.zeros_like(loss)), rank, torch.stack([lse, c, s, sm], 1)
+
+
+def xent_robust_bwd(logits, labels, C, rec, mode, lam, table, idx, grad_out, scale, out_bf16):
+    B, ld = logits.shape
+    x, a, i, valid, _, _ = _robust_rows(logits, labels, C, mode, table, idx)
+    lse, c, s, sm = rec.unbind(1)
+    p = torch.exp(x - lse.unsqueeze(1))
+    d = p.clone()
+    d.scatter_add_(1, a.clamp(0, C - 1).view(-1, 1), torch.full((B, 1), -1.0))
+    if mode == 2:
+        t = table[i.clamp(0, table.shape[0] - 1)]
+        inside = ((p > _ELR_LO) & (p < _ELR_HI)).float()
+        d = d - (lam / (1 - s)).unsqueeze(1) * p * (inside * t - sm.unsqueeze(1))
+    g = float(grad_out.float().reshape(-1)[0]) * scale
+    out = torch.zeros(B, ld)
+    out[:, :C] = torch.where(valid.view(-1, 1), d * (g * c).unsqueeze(1), torch.zeros_like(d))
+    return out.to(torch.bfloat16 if out_bf16 else torch.float32)
+
+
 def log_softmax_fwd(x, C):
     return torch.log_softmax(_f(x)[:, :C], 1)
 

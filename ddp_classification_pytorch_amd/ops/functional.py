@@ -1642,15 +1642,77 @@ class _XEntMix(Function):
         return d, None, None, None, None, None, None
 
 
-def cross_entropy(logits, labels, num_classes=None, smoothing=0.0, reduction="mean", return_rank=False, mix=None):
+_ROBUST_MODES = {"gce": 0, "sce": 1, "elr": 2}
+
+
+def _robust_plan(robust):
+    """``robust`` of :func:`cross_entropy` -> (mode, a0, a1, table, idx)."""
+    name = robust[0] if isinstance(robust, (tuple, list)) and robust else robust
+    want = {"gce": 2, "sce": 3, "elr": 5}.get(name)
+    if want is None or len(robust) != want:
+        raise ValueError('cross_entropy robust covers ("gce", q), ("sce", alpha, beta) and '
+                         f'("elr", lam, mom, table, idx), got {robust!r}')
+    if name == "gce":
+        if not 0.0 < float(robust[1]) <= 1.0:
+            raise ValueError(f"cross_entropy robust covers gce with 0 < q <= 1, got q = {robust[1]}")
+        return 0, float(robust[1]), 0.0, None, None
+    if name == "sce":
+        return 1, float(robust[1]), float(robust[2]), None, None
+    return 2, float(robust[1]), float(robust[2]), robust[3], robust[4].to(torch.int64).contiguous()
+
+
+class _XEntRobust(Function):
+    """GCE / SCE / ELR (``xent_robust_fwd`` / ``xent_robust_bwd``, csrc/loss_robust.hip): the forward saves the
+    row record (lse, c, s, s_m), so the backward is one streaming pass.  Under elr the forward updates
+    ``table`` in place at the rows ``idx``; the table is a constant for autograd."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, C, mode, a0, a1, table, idx, reduction):
+        loss_rows, rank, rec = K(logits).xent_robust_fwd(logits, labels, C, mode, a0, a1, table, idx)
+        if mode == 2:
+            ctx.save_for_backward(logits, labels, rec, table, idx)
+        else:
+            ctx.save_for_backward(logits, labels, rec)
+        ctx.C, ctx.mode, ctx.a0, ctx.reduction = C, mode, a0, reduction
+        ctx.mark_non_differentiable(rank)
+        ctx.set_materialize_grads(False)
+        loss = loss_rows.mean() if reduction == "mean" else loss_rows.sum()
+        return loss, rank
+
+    @staticmethod
+    def backward(ctx, g, _grank):
+        if g is None:
+            return (None,) * 9
+        logits, labels, rec = ctx.saved_tensors[:3]
+        table, idx = ctx.saved_tensors[3:] if ctx.mode == 2 else (None, None)
+        scale = 1.0 / logits.shape[0] if ctx.reduction == "mean" else 1.0
+        d = K(logits).xent_robust_bwd(logits, labels, ctx.C, rec, ctx.mode, ctx.a0, table, idx, g.reshape(1), scale,
+                                      logits.dtype == torch.bfloat16)
+        return (d,) + (None,) * 8
+
+
+def cross_entropy(logits, labels, num_classes=None, smoothing=0.0, reduction="mean", return_rank=False, mix=None,
+                  robust=None):
     """Softmax cross-entropy (one fused pass) -> loss [, rank of the true label].
+
+    ``robust`` selects a noise-robust loss (csrc/loss_robust.hip): ``("gce", q)`` with 0 < q <= 1,
+    ``("sce", alpha, beta)`` or ``("elr", lam, mom, table, idx)``.  For elr ``table`` is the fp32
+    [N_train, C] target table on the logits' device, zero at the start of training and updated in place by
+    every forward, and ``idx`` (int64 [B]) the dataset index of each row; the indices of one batch must
+    be distinct (not checked on the device: a duplicate makes two rows race for one table row).
+    ``robust`` covers neither ``mix`` nor ``smoothing > 0``.
 
     ``mix=(partner, wlab)`` (int32 [B], fp32 [B]; data/mix.py) is the loss of a Mixup / CutMix batch:
     row b carries ``labels[b]`` with weight ``wlab[b]`` and ``labels[partner[b]]`` with
     ``1 - wlab[b]``.  The rank it returns is that of the row's OWN label, so training top-1 / top-3
     under mixing are measured against the own label.  Without ``mix`` the one-label kernels run."""
     C = num_classes or logits.shape[1]
-    if mix is not None:
+    if robust is not None:
+        if mix is not None or float(smoothing) > 0:
+            raise ValueError("cross_entropy robust covers one hard label per row: neither mix nor smoothing > 0")
+        mode, a0, a1, table, idx = _robust_plan(robust)
+        loss, rank = _XEntRobust.apply(logits, labels, C, mode, a0, a1, table, idx, reduction)
+    elif mix is not None:
         partner, wlab = mix
         loss, rank = _XEntMix.apply(logits, labels, partner, wlab, C, float(smoothing), reduction)
     else:
