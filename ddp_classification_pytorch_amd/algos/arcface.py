@@ -20,6 +20,10 @@ other validation embeddings (``evaluate_knn_vote``).
 row against the batch's labels and a share R of the other classes, drawn on the device; each rank
 samples against its own labels and the dense weight gradient is all-reduced as ever.  Evaluation
 keeps the full head.
+
+``--arc-supcon-weight W`` > 0 adds W times the in-batch supervised contrastive loss
+(``Fn.supcon_loss``, ``--arc-supcon-temperature``) of the embedding the head receives to the step's
+loss.  It is taken over each rank's local batch: no cross-rank negatives, the scope Mixup has.
 """
 from __future__ import annotations
 
@@ -36,15 +40,19 @@ from ..parallel.ddp import attach_optimizer, wrap_ddp
 
 
 class ArcFaceModel(nn.Module):
-    def __init__(self, backbone, embed_head, arc):
+    def __init__(self, backbone, embed_head, arc, supcon_weight=0.0, supcon_temperature=0.07):
         super().__init__()
         self.backbone, self.embed, self.arc = backbone, embed_head, arc
+        self.supcon_weight, self.supcon_temperature = float(supcon_weight), float(supcon_temperature)
 
     def features(self, x):
         return self.embed(self.backbone.forward_features(x))
 
     def forward(self, x, labels):
-        loss, rank, _ = self.arc(self.features(x), labels)
+        f = self.features(x)
+        loss, rank, _ = self.arc(f, labels)
+        if self.supcon_weight > 0:  # (0: no new kernel runs, every bit as before)
+            loss = loss + self.supcon_weight * Fn.supcon_loss(f.contiguous(), labels.long(), self.supcon_temperature)
         return loss, rank
 
 
@@ -57,7 +65,8 @@ def build_arcface(args):
     embed = MLPHead(backbone.feat_dim, args.hidden, args.embed_dim, log_softmax=True)
     arc = ArcMarginProduct(args.embed_dim, args.num_classes, s=args.arc_s, m=args.arc_m, easy_margin=args.easy_margin,
                            sub_centers=args.arc_sub_centers, sample_rate=getattr(args, "arc_sample_rate", 1.0))
-    return ArcFaceModel(backbone, embed, arc)
+    return ArcFaceModel(backbone, embed, arc, getattr(args, "arc_supcon_weight", 0.0),
+                        getattr(args, "arc_supcon_temperature", 0.07))
 
 
 def run(args):

@@ -53,7 +53,9 @@ FILE_FLAGS = {"stem.hip": ["-fno-slp-vectorize"],
               "arcface_sub.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the top-k selection's compares and selects run beside the MFMAs as well
               "knn.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
-              "knn_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "knn_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the contrastive loss's softmax tail (two exps per score) sits between its MFMA groups
+              "supcon.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _headers():

@@ -207,6 +207,10 @@ def build_parser() -> argparse.ArgumentParser:
     a("--arc-sample-rate", type=float, default=1.0,
       help="Partial FC: each training step scores a row against the batch's labels and this share of the other "
            "classes, drawn on the device (1.0: the full head; not with --arc-sub-centers > 1)")
+    a("--arc-supcon-weight", type=float, default=0.0,
+      help="adds W times the in-batch supervised contrastive loss of the embedding (each rank's local batch) to the "
+           "ArcFace loss (0: off)")
+    a("--arc-supcon-temperature", type=float, default=0.07, help="temperature of --arc-supcon-weight")
     # CDR (unused reference flags accepted for CLI compatibility)
     a("--noise_rate", "--noise-rate", dest="noise_rate", type=float, default=0.2)
     a("--num_gradual", type=int, default=10)
@@ -352,6 +356,9 @@ def refuse_knn(args, workload: str):
     if float(getattr(args, "arc_sample_rate", 1.0)) != 1.0:
         raise ValueError(f"--arc-sample-rate: Partial FC is wired for --workload arcface only; the {workload} "
                          f"workload has no ArcFace head")
+    if float(getattr(args, "arc_supcon_weight", 0.0)) != 0.0:
+        raise ValueError(f"--arc-supcon-weight: the contrastive loss is wired for --workload arcface only; the "
+                         f"{workload} workload has no embedding head")
 
 
 def check_knn(args):
@@ -362,6 +369,10 @@ def check_knn(args):
     if r < 1.0 and int(getattr(args, "arc_sub_centers", 1)) > 1:
         raise ValueError("--arc-sample-rate < 1 covers --arc-sub-centers 1 only (the sampled head has no sub-centre "
                          "kernel)")
+    if float(getattr(args, "arc_supcon_weight", 0.0)) < 0:
+        raise ValueError(f"--arc-supcon-weight covers W >= 0 (0: off), got {args.arc_supcon_weight}")
+    if float(getattr(args, "arc_supcon_weight", 0.0)) > 0 and not float(getattr(args, "arc_supcon_temperature", 0.07)) > 0:
+        raise ValueError(f"--arc-supcon-temperature must be positive, got {args.arc_supcon_temperature}")
     k = int(getattr(args, "arc_eval_knn", 0) or 0)
     if not 0 <= k <= 8:
         raise ValueError(f"--arc-eval-knn covers 1 <= K <= 8 (0: off), got {k}")

@@ -467,6 +467,16 @@ bool launch_arcface_l2norm_t(const void* x, bool is_bf16, int R, int D, int Rp, 
   return true;
 }
 
+void launch_arc_norm_bwd(const float* part, int S, size_t sstride, const bf16* y, int Dp, int D, const float* inv,
+                         int R, void* out, bool out_bf16, hipStream_t st) {
+  if (out_bf16)
+    hipLaunchKernelGGL(arc_norm_bwd_kernel<bf16>, dim3(R), dim3(256), 0, st, part, S, sstride, y, Dp, D, inv,
+                       (bf16*)out);
+  else
+    hipLaunchKernelGGL(arc_norm_bwd_kernel<float>, dim3(R), dim3(256), 0, st, part, S, sstride, y, Dp, D, inv,
+                       (float*)out);
+}
+
 int arcface_fused_fwd_splits(int Bp, int Cp) {
   return score_splits(Bp / 64, Cp / kArcTile, 1024, 64);
 }
@@ -517,13 +527,7 @@ bool launch_arcface_fused_dx(const bf16* xn, const bf16* wn, const bf16* wnT, co
   hipLaunchKernelGGL((arc_rows_kernel<KS_, 1>), grid, dim3(256), lds, st, p);
   if (Dp == 128) { ARC_DX(4) } else if (Dp == 256) { ARC_DX(8) } else { ARC_DX(16) }
 #undef ARC_DX
-  const size_t ss = (size_t)Bp * Dp;
-  if (dx_bf16)
-    hipLaunchKernelGGL(arc_norm_bwd_kernel<bf16>, dim3(B), dim3(256), 0, st, part, p.S, ss, xn, Dp, D, inv_x,
-                       (bf16*)dx);
-  else
-    hipLaunchKernelGGL(arc_norm_bwd_kernel<float>, dim3(B), dim3(256), 0, st, part, p.S, ss, xn, Dp, D, inv_x,
-                       (float*)dx);
+  launch_arc_norm_bwd(part, p.S, (size_t)Bp * Dp, xn, Dp, D, inv_x, B, dx, dx_bf16, st);
   return true;
 }
 

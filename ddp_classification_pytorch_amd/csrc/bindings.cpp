@@ -2391,6 +2391,53 @@ std::tuple<Tensor, Tensor, Tensor> knn_topk(const Tensor& qn, const Tensor& gn, 
   return {val, idx, hit};
 }
 
+// Fused supervised contrastive loss (supcon.hip): zn [Bp][Dp] from arcface_l2norm_t, labels int64 [B].
+// splits: 1..64 column splits, 0 = the heuristic.  -> (rec [Bp][4] = (lse, 1 / |P| or 0, label bits, loss_i),
+// stat [2] = (mean loss over the anchors, 1 / max(1, #anchors)), nanch int32 [1] = #anchors)
+std::tuple<Tensor, Tensor, Tensor> supcon_fwd(const Tensor& zn, const Tensor& labels, int64_t B, double tau,
+                                              int64_t splits) {
+  CHECK_ACT(zn);
+  const int Bp = zn.size(0), Dp = zn.size(1);
+  TORCH_CHECK(labels.scalar_type() == at::kLong && labels.is_cuda() && labels.is_contiguous() && labels.numel() == B,
+              "supcon_fwd: labels int64 [B]");
+  const int S = splits > 0 ? (int)splits : dcp::supcon_fwd_splits(Bp);
+  TORCH_CHECK(splits >= 0 && S <= 64, "supcon_fwd: 1 <= splits <= 64, got ", splits);
+  auto y32 = at::empty({Bp}, zn.options().dtype(at::kInt));
+  auto part = at::empty({(int64_t)S * Bp * 4}, f32_like(zn));
+  auto rec = at::empty({Bp, 4}, f32_like(zn));
+  auto stat = at::empty({2}, f32_like(zn));
+  auto nanch = at::empty({1}, zn.options().dtype(at::kInt));
+  TORCH_CHECK(dcp::launch_supcon_fwd(bp(zn), labels.data_ptr<int64_t>(), (int)B, Bp, Dp, (float)tau, S,
+                                     y32.data_ptr<int>(), part.data_ptr<float>(), rec.data_ptr<float>(),
+                                     stat.data_ptr<float>(), nanch.data_ptr<int>(), cur_stream()),
+              "supcon_fwd: unsupported shape (1 <= B <= Bp, Bp % 64, Dp in {128, 256, 512}, tau > 0)");
+  return {rec, stat, nanch};
+}
+
+// -> dx [B][D] (fp32 or bf16): the gradient of grad_out[0] * (mean loss) through the normalisation
+Tensor supcon_dz(const Tensor& zn, const Tensor& znT, const Tensor& inv, const Tensor& rec, const Tensor& stat,
+                 const Tensor& grad_out, int64_t B, int64_t D, double tau, int64_t splits, bool out_bf16) {
+  CHECK_ACT(zn);
+  CHECK_ACT(znT);
+  const int Bp = zn.size(0), Dp = zn.size(1);
+  TORCH_CHECK(znT.size(0) == Dp && znT.size(1) == Bp, "supcon_dz: znT [Dp][Bp]");
+  TORCH_CHECK(rec.is_cuda() && rec.scalar_type() == at::kFloat && rec.is_contiguous() && rec.numel() == (int64_t)Bp * 4 &&
+                  stat.is_cuda() && stat.scalar_type() == at::kFloat && stat.numel() == 2 && inv.is_cuda() &&
+                  inv.scalar_type() == at::kFloat && inv.is_contiguous() && inv.numel() == Bp,
+              "supcon_dz: rec [Bp][4], stat [2], inv [Bp] fp32");
+  const int S = splits > 0 ? (int)splits : dcp::supcon_dz_splits(Bp);
+  TORCH_CHECK(splits >= 0 && S <= 64, "supcon_dz: 1 <= splits <= 64, got ", splits);
+  auto g = grad_out.to(at::kFloat).contiguous();
+  TORCH_CHECK(g.is_cuda() && g.numel() == 1, "supcon_dz: grad_out [1]");
+  auto part = at::empty({(int64_t)S * Bp * Dp}, f32_like(zn));
+  auto dx = at::empty({B, D}, zn.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+  TORCH_CHECK(dcp::launch_supcon_dz(bp(zn), bp(znT), rec.data_ptr<float>(), stat.data_ptr<float>(), g.data_ptr<float>(),
+                                    inv.data_ptr<float>(), (int)B, Bp, Dp, (int)D, (float)tau, S,
+                                    part.data_ptr<float>(), dx.data_ptr(), out_bf16, cur_stream()),
+              "supcon_dz: unsupported shape (1 <= B <= Bp, Bp % 64, D <= Dp in {128, 256, 512}, tau > 0)");
+  return dx;
+}
+
 int64_t knn_wide_splits(int64_t Nqp, int64_t Ngp) { return dcp::knn_wide_splits((int)Nqp, (int)Ngp); }
 
 // the same for 1 <= k <= 256 (knn_wide.hip) -> (val [Nq][k] fp32, idx [Nq][k] int32)
@@ -2931,6 +2978,9 @@ TORCH_LIBRARY(dcp, m) {
   m.def("knn_splits(int Nqp, int Ngp) -> int", &knn_splits);
   m.def("knn_topk(Tensor qn, Tensor gn, int Nq, int Ng, int k, int splits, Tensor? exclude, Tensor? q_labels, "
         "Tensor? g_labels) -> (Tensor, Tensor, Tensor)", &knn_topk);
+  m.def("supcon_fwd(Tensor zn, Tensor labels, int B, float tau, int splits) -> (Tensor, Tensor, Tensor)", &supcon_fwd);
+  m.def("supcon_dz(Tensor zn, Tensor znT, Tensor inv, Tensor rec, Tensor stat, Tensor grad_out, int B, int D, float tau, "
+        "int splits, bool out_bf16) -> Tensor", &supcon_dz);
   m.def("knn_wide_splits(int Nqp, int Ngp) -> int", &knn_wide_splits);
   m.def("knn_topk_wide(Tensor qn, Tensor gn, int Nq, int Ng, int k, int splits, Tensor? exclude) -> (Tensor, Tensor)",
         &knn_topk_wide);

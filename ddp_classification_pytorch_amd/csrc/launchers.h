@@ -491,6 +491,22 @@ bool launch_arcface_fused_dw(const bf16* xn, const bf16* xnT, const bf16* wn, co
 // head's rule); false: by its low 32 bits read as int (the plain head's).
 void launch_arc_fwd_finalize(const float* part, int S, int B, int Bp, int C, const int64_t* labels, const float* lab,
                              float* loss, int* rank, float* lse, bool label64, hipStream_t st);
+// The split merge + L2-normalisation backward the dX kernels share (arcface.hip): rows r < R,
+// g = sum_s part[s * sstride + r * Dp + :D], out [R][D] (fp32 or bf16) = inv[r] (g - y[r] <g, y[r]>)
+void launch_arc_norm_bwd(const float* part, int S, size_t sstride, const bf16* y, int Dp, int D, const float* inv,
+                         int R, void* out, bool out_bf16, hipStream_t st);
+// Fused in-batch supervised contrastive loss (supcon.hip): no [B, B] tensor.  zn [Bp][Dp] / znT [Dp][Bp] /
+// inv [Bp] from launch_arcface_l2norm_t, 1 <= S <= 64 column splits (supcon_*_splits: the heuristics).
+// fwd: y32 [Bp] and part [S][Bp][4] are scratch; rec [Bp][4] = (lse, 1 / |P| or 0 for a non-anchor, label
+// bits, loss_i), stat [2] = (mean loss over the anchors, 1 / max(1, #anchors)), nanch [1] = #anchors.
+// dz: part [S][Bp][Dp] is scratch; gout [1] the upstream gradient; dx [B][D].  false = unsupported.
+int supcon_fwd_splits(int Bp);
+int supcon_dz_splits(int Bp);
+bool launch_supcon_fwd(const bf16* zn, const int64_t* labels, int B, int Bp, int Dp, float tau, int S, int* y32,
+                       float* part, float* rec, float* stat, int* nanch, hipStream_t st);
+bool launch_supcon_dz(const bf16* zn, const bf16* znT, const float* rec, const float* stat, const float* gout,
+                      const float* inv, int B, int Bp, int Dp, int D, float tau, int S, float* part, void* dx,
+                      bool dx_bf16, hipStream_t st);
 // Fused Sub-center ArcFace head (arcface_sub.hip): K in {2, 3, 4} centres per class, Dp in {128, 256}.
 // The centre operands wn [Wp][Dp], wnT [Dp][Wp], inv_w [Wp] use the planar row order of that file,
 // Wp = arcface_sub_rows(C, K); xn / xnT / inv_x come from launch_arcface_l2norm_t.  The partial buffers

@@ -1012,6 +1012,25 @@ def arcface_sub_head(x, weight, labels, s, m, easy):
     return loss, rank, sub, logits
 
 
+def supcon_loss(x, labels, tau):
+    """Reference math of the fused supervised contrastive loss (csrc/supcon.hip), differentiable torch
+    ops in fp32: a row is valid with a label in [0, 2^31); A(i) = the valid rows but i, P(i) = those of
+    A(i) with i's label; loss = mean over the anchors (valid rows with a positive) of
+    lse_{a in A(i)} s_ia - mean_{p in P(i)} s_ip, s = cos / tau; 0 without any anchor."""
+    z = F.normalize(_f(x), dim=1, eps=1e-12)
+    y = labels.long().view(-1)
+    valid = (y >= 0) & (y < 2 ** 31)
+    pair = valid.view(-1, 1) & valid.view(1, -1) & ~torch.eye(len(y), dtype=torch.bool, device=y.device)
+    pos = pair & (y.view(-1, 1) == y.view(1, -1))
+    cnt = pos.sum(1)
+    anchor = cnt > 0
+    s = z @ z.t() / tau
+    # (a non-anchor's row is all zeros before the logsumexp: no -inf row, no NaN gradient)
+    lse = torch.logsumexp(torch.where(anchor.view(-1, 1), s.masked_fill(~pair, -math.inf), torch.zeros_like(s)), 1)
+    rows = torch.where(anchor, lse - (s * pos).sum(1) / cnt.clamp(min=1), torch.zeros_like(lse))
+    return rows.sum() / anchor.sum().clamp(min=1)
+
+
 def knn_prep(x, Rp, Dp, normalize, eps):
     xf = F.normalize(_f(x), dim=1, eps=eps) if normalize else _f(x)
     return F.pad(xf, (0, Dp - x.shape[1], 0, Rp - x.shape[0])).bfloat16()

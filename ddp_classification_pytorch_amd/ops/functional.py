@@ -2089,6 +2089,69 @@ def arcface_partial_loss(x, weight, labels, s=30.0, m=0.5, easy_margin=True, sam
     return loss, rank, idx
 
 
+# ----------------------------------------------------------------------------- contrastive
+class _SupCon(Function):
+    """The in-batch supervised contrastive loss without a [B, B] tensor (csrc/supcon.hip): forward
+    streams the batch's own normalised rows past each 64-row anchor block (online log-sum-exp, positive
+    sum and count per row), backward recomputes each score tile and forms dS_ia + dS_ai from the saved
+    row records in the accumulators, the second MFMA's operand."""
+
+    @staticmethod
+    def forward(ctx, x, labels, tau, splits):
+        k = K(x)
+        B, D = x.shape
+        zn, znT, inv = k.arcface_l2norm_t(x.contiguous(), round_up(B, 64), arcface_fused_dp(D), 1e-12)
+        rec, stat, _ = k.supcon_fwd(zn, labels, B, tau, splits)
+        ctx.save_for_backward(zn, znT, inv, rec, stat)
+        ctx.cfg = (B, D, tau, splits, x.dtype == torch.bfloat16)
+        ctx.set_materialize_grads(False)
+        return stat[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        zn, znT, inv, rec, stat = ctx.saved_tensors
+        B, D, tau, splits, x_bf16 = ctx.cfg
+        return K(zn).supcon_dz(zn, znT, inv, rec, stat, g.reshape(1), B, D, tau, splits, x_bf16), None, None, None
+
+
+SUPCON_MAX_D = 512
+
+
+def supcon_loss(x, labels, temperature=0.07, splits=None):
+    """In-batch supervised contrastive loss (Khosla et al. 2020, L_out^sup) of the rows of ``x`` [B, D]
+    (fp32 or bf16, D <= 512) with int64 ``labels`` [B] -> the fp32 mean over the anchors.
+
+    Rows are L2-normalised as the fused ArcFace heads normalise; s = cos / temperature.  A row with a
+    label outside [0, 2^31) is neither an anchor nor a negative; an anchor is a valid row with at least
+    one other valid row of its label, and its loss is log sum_{a != i} exp(s_ia) - mean_{p} s_ip.  A
+    batch without any positive pair gives 0 and zero gradients.  With ``arange(N)`` twice as labels and
+    ``cat(view1, view2)`` as rows this is NT-Xent; with labels repeated per view multi-view SupCon.
+
+    On the GPU the fused kernels of csrc/supcon.hip (bf16 operands, fp32 MFMA scores consumed in
+    registers, nothing [B, B] written, nothing read on the host: capturable); ``splits`` (1..64, default
+    a heuristic) is the number of column splits.  On the CPU the torch math of ``_ref.supcon_loss``."""
+    if x.dim() != 2 or not x.is_contiguous() or x.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"supcon_loss covers contiguous fp32 or bf16 rows [B, D], got {x.dtype} {tuple(x.shape)}")
+    B, D = x.shape
+    if B < 2:
+        raise ValueError(f"supcon_loss covers 2 <= B, got B = {B}")
+    if not 1 <= D <= SUPCON_MAX_D:
+        raise ValueError(f"supcon_loss covers 1 <= D <= {SUPCON_MAX_D}, got D = {D}")
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.numel() != B or labels.device != x.device:
+        raise ValueError(f"supcon_loss covers int64 labels [B] on the rows' device, got {labels.dtype} "
+                         f"{tuple(labels.shape)} on {labels.device}")
+    tau = float(temperature)
+    if not tau > 0:
+        raise ValueError(f"supcon_loss covers temperature > 0, got {temperature}")
+    if splits is not None and not 1 <= int(splits) <= 64:
+        raise ValueError(f"supcon_loss covers 1 <= splits <= 64, got {splits}")
+    if not x.is_cuda:
+        return _ref.supcon_loss(x, labels, tau)
+    return _SupCon.apply(x, labels.contiguous(), tau, int(splits or 0))
+
+
 # ----------------------------------------------------------------------------- retrieval
 KNN_MAX_K = 8
 KNN_MAX_D = 512
